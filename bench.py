@@ -6,13 +6,19 @@ rumors at their Philox origins, then push-pull rounds (fanout 2) until every
 node holds every rumor.  node-updates = nodes x rounds.  The workload is the
 north-star sweep, configs[3]: 2^27 nodes, push-pull k=2, R=64, seed
 0x5EED0004, at every GPU count (1/2/4/8 GPUs, strong
-scaling; N > 1 shards the node ids).  At one GPU the configs[2]
-workload (2^24 nodes, seed 0x5EED0003) is timed beside it as `secondary`, and
-configs[4] (anti-entropy with churn, 2^26 nodes x 16 versions) as `antientropy`.
+scaling; N > 1 shards the node ids).
 State is resident in HBM; nothing crosses PCIe in the timed region except the
 per-round 8-byte-per-rumor stats readback.
 
-Single GPU:  python bench.py [--steps K --warmup W]
+A plain one-GPU run sets up, warms up, times the steps and prints its line
+(headline and the roofline figures the timed steps' own timers give).  --full
+adds what takes runs or checks of its own: the comparison with the oracle
+fixture (`verified`), the all-dense run, the configs[2] workload (2^24 nodes,
+seed 0x5EED0003) as `secondary`, configs[4] (anti-entropy with churn, 2^26
+nodes x 16 versions) as `antientropy`, and the CPU baseline.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
+
+Single GPU:  python bench.py [--steps K --warmup W] [--full] [--dump-outputs DIR]
 N GPUs:      python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 Weak scaling instead (fixed nodes per GPU): --nodes-per-gpu M
 """
@@ -346,6 +352,30 @@ def antientropy_run(device: int, steps: int, warmup: int) -> dict:
             "state_hash": False}
 
 
+DUMP_SAMPLE_NODES = 4096
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(path: str, eng, stats: list, final_hash: int) -> None:
+    """What the last timed step handed its caller, as float64 / float32 .npy files (a few MB at most):
+    round_stats  [rounds, len(STAT_KEYS)]: the per-round stats gossip_step returned (STAT_KEYS order)
+    state_hash   [4]: the state hash of the state the step left, as 16-bit limbs, low first
+    state_sample [DUMP_SAMPLE_NODES, 1 + rumors]: node id, then one 0/1 per rumor the node holds, for a
+                 fixed seeded sample of this process's nodes (the whole state is 8 B x nodes)"""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "round_stats.npy"),
+            np.array([[s[k] for k in STAT_KEYS] for s in stats], dtype=np.float64).reshape(len(stats), len(STAT_KEYS)))
+    np.save(os.path.join(path, "state_hash.npy"),
+            np.array([(final_hash >> (16 * i)) & 0xFFFF for i in range(4)], dtype=np.float64))
+    ids = eng.lo + np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, eng.hi - eng.lo, size=DUMP_SAMPLE_NODES)
+    sample = np.zeros((DUMP_SAMPLE_NODES, 1 + RUMORS), dtype=np.float64)
+    for row, node in zip(sample, ids):
+        words = eng.read_bitset(int(node))
+        row[0] = node
+        row[1:] = [(int(words[r // 64]) >> (r % 64)) & 1 for r in range(RUMORS)]
+    np.save(os.path.join(path, "state_sample.npy"), sample)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -354,10 +384,16 @@ def main():
     ap.add_argument("--nodes", type=int, default=NODES_TOTAL, help="total nodes (strong scaling; default 2^27)")
     ap.add_argument("--nodes-per-gpu", type=int, default=0, help="weak scaling: this many nodes per GPU")
     ap.add_argument("--seed", type=lambda x: int(x, 0), default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-dense-only", action="store_true", help="skip the all-dense comparison run (profiling)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[2] line (profiling)")
-    ap.add_argument("--no-antientropy", action="store_true", help="skip the configs[4] line (profiling)")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: beside the headline, check the run against the oracle fixture and run the "
+                         "all-dense comparison, configs[2], configs[4] and the CPU baseline (each has a --no-... "
+                         "switch); N > 1 lines are always checked")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-dense-only", action="store_true", help="--full without the all-dense comparison run")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the configs[2] line")
+    ap.add_argument("--no-antientropy", action="store_true", help="--full without the configs[4] line")
     ap.add_argument("--place-tries", type=int, default=0,
                     help="engine param place_tries (0: the engine's default; 1: no placement trial rounds, "
                          "for PMC passes that should count only the workload's rounds)")
@@ -427,9 +463,12 @@ def main():
             return eng.step(64, with_infected=False).stats
         return sharded_run(eng, 64, trace=trace)
 
-    fx = load_fixture(n_total, seed)
+    checked = args.full or world > 1  # a plain one-GPU run times its steps and leaves the comparison to --full
+    fx = load_fixture(n_total, seed) if checked else None
 
     def verify(stats):
+        if not checked:
+            return "not checked: --full compares the run with the oracle fixture"
         if fx is None:
             return "no oracle fixture for this workload"
         return check_run(stats, global_state_hash(eng, world, args.backend), fx)
@@ -487,6 +526,10 @@ def main():
     # after the timed region: the last timed step against the oracle's run of the same workload
     final_check = verify(last) if last is not None else "no timed step"
     verified = None if fx is None or last is None else final_check is None
+    if args.dump_outputs and last is not None:
+        final_hash = global_state_hash(eng, world, args.backend)  # collective: every rank calls it
+        if rank == 0:
+            dump_outputs(args.dump_outputs, eng, last, final_hash)
 
     total_rounds = sum(rounds)
     value = n_total * total_rounds / dt
@@ -539,13 +582,14 @@ def main():
             **({"backend": "gloo (rehearsal: not a measurement)"} if world > 1 and args.backend == "gloo" else {}),
             "roofline": rl,
         }
-        if world == 1 and not args.no_dense_only:
+        extras = world == 1 and args.full
+        if extras and not args.no_dense_only:
             rl["dense_only"] = dense_only(n_total, seed, local)
-        if world == 1 and not args.no_secondary and n_total != NODES_SECONDARY:
+        if extras and not args.no_secondary and n_total != NODES_SECONDARY:
             out["secondary"] = secondary_run(local, max(args.steps, 5), max(args.warmup, 2))
-        if world == 1 and not args.no_antientropy and not per_gpu and n_total == NODES_TOTAL:
+        if extras and not args.no_antientropy and not per_gpu and n_total == NODES_TOTAL:
             out["antientropy"] = antientropy_run(local, 3, 1)
-        if world == 1 and not args.no_cpu_baseline:
+        if extras and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(n_total, seed)
         print(json.dumps(out), flush=True)
     if world > 1:

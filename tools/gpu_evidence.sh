@@ -14,7 +14,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; ok $?
   tail -1 $O/smoke.txt
 fi
-timeout -k 10 400 python bench.py --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err; ok $?
+timeout -k 10 400 python bench.py --steps 10 --warmup 3 --full > $O/bench.json 2> $O/bench.err; ok $?
 cat $O/bench.json
 P="--no-cpu-baseline --no-dense-only --no-secondary --no-antientropy"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python bench.py --steps 10 --warmup 3 $P > $O/prof.out 2>&1; ok $?

@@ -6,7 +6,7 @@ set -u
 O=gpurun_out/${1:-pmc_sq}
 mkdir -p $O
 export TMPDIR=/tmp
-B=${BENCH:-python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-dense-only}
+B=${BENCH:-python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-dense-only}
 i=0
 for grp in \
   "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR GRBM_GUI_ACTIVE" \
