@@ -95,7 +95,6 @@ __device__ __forceinline__ uint32_t id_of_dst(uint32_t d) {
 __device__ __forceinline__ uint32_t id_of_src(uint32_t s) {
   return ((s & kIdNMask) << kTileDLog) | ((s & kSrcVF) ? kIdVF : 0u);
 }
-__device__ __forceinline__ uint32_t id_of_pair(uint32_t d, uint32_t s) { return id_of_dst(d) | id_of_src(s); }
 
 __device__ __forceinline__ uint32_t xcd_remap(uint32_t b, uint32_t n) {
   // blocks are dealt round-robin over the 8 XCDs: give each XCD a contiguous
@@ -191,7 +190,11 @@ __device__ __forceinline__ uint32_t region_offsets(uint32_t* cur, uint32_t nt, u
 // cur[d >> 1]; regions of <= 32768 records, so no half overflows)
 __device__ __forceinline__ uint32_t region_offsets_packed(uint32_t* cur, uint32_t nt, uint16_t* off_row,
                                                           uint32_t* wsum, uint32_t* wpre) {
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // an opaque copy of the lane index per call: the thread's word range and its loop bounds are
+  // derived again in each region, not hoisted out of the emit's region loop and spilled
+  uint32_t tid;
+  __asm__ volatile("" : "=v"(tid) : "0"(threadIdx.x));
+  const uint32_t lane = tid & 63, wave = tid >> 6;
   const uint32_t nw = (nt + 1) >> 1;  // this thread: whole words [lo, hi)
   const uint32_t per = (nw + kEmitThreads - 1) / kEmitThreads;
   const uint32_t lo = min(tid * per, nw), hi = min(lo + per, nw);
@@ -265,7 +268,7 @@ __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const
   __shared__ uint32_t wsum[kEmitThreads / 64];
   __shared__ uint32_t wpre[kEmitThreads / 64 + 1];
 
-  const uint32_t tid = threadIdx.x;
+  uint32_t tid = threadIdx.x;
   const uint64_t nm1 = g.N - 1, fm = full_mask1(R);
   constexpr uint32_t kQ = kMaxS / kEmitThreads;  // senders per thread upper bound
   const uint64_t snd0 = SHARD ? er.snd0 : 0ull, nsnd = SHARD ? er.nsnd : g.N;
@@ -322,6 +325,10 @@ __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const
     r = s_claim;
   }
   if (r >= nr) break;
+  // big regions: an opaque copy of the lane index per region, so that the values derived from
+  // it (16 sender indices, 32 record offsets per lane) are computed again in each region, not
+  // hoisted out of the region loop and spilled
+  if constexpr (BIG) __asm__ volatile("" : "=v"(tid) : "0"(threadIdx.x));
   const uint32_t s = region(r);
   const uint64_t base = (uint64_t)s << g.ts_log;
   const uint32_t nsend = (uint32_t)min<uint64_t>(g.ts, nsnd - base);
@@ -524,38 +531,56 @@ __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const
     // push is written packed {value, id} (BinGeom::aos), its value read from LDS: the
     // values are the ones in v[] (no second read of S), and no record gathers its
     // sender's word from L2 / MALL (a 64-B fetch per 8-B value at 2^27 nodes: emit 158 B
-    // of fetch per node, profiles/r03_a/pmc_dense_2p27.json).  The ids are read back from
-    // the region just written (plain stores: L2-resident; a register copy of 32 ids per
-    // lane spilled 39 VGPRs).
-    for (uint32_t e = tid; e < total; e += kEmitThreads) {
-      const uint32_t id = st_ids[e];
-      if (split) {
-        gdst[e] = dst_of(id);
-        gsrc[e] = src_of(id);
-      } else {
-        gids[e] = id;
-      }
-    }
-    if constexpr (!NOVALS) {
-      __syncthreads();  // every staged id is out
+    // of fetch per node, profiles/r03_a/pmc_dense_2p27.json).  The staged ids wait in
+    // registers meanwhile (record e = lane + j * kEmitThreads in idr[j]), so every field
+    // of a record is written in one loop and nothing is read back from the region: the
+    // read-back missed L2 (18.5 M -> 8.4 M memory read requests per 2^27 launch, emit 1492 ->
+    // 1136 us: profiles/emit_onchip/).
+    if constexpr (NOVALS) {  // V = 7, 9: ids only, straight from the staging room
+      for (uint32_t e = tid; e < total; e += kEmitThreads) rec_st(&gids[e], st_ids[e]);
+    } else {
+      constexpr uint32_t kIdsPerLane = 2 * kRecPerRegion / kEmitThreads;
+      constexpr uint32_t kGroup = 4;  // records per lane whose LDS value loads fly together
+      // (a fresh opaque copy for the loads and another for the stores: the 32 record offsets
+      // of the loads do not stay live beside the ids until the stores)
+      uint32_t lid;
+      __asm__ volatile("" : "=v"(lid) : "0"(tid));
+      uint32_t idr[kIdsPerLane];
+      // never a branch around a load, and no clamp either: every slot lies inside st_ids,
+      // and a slot past `total` (stale) is masked to a sender index inside sv and not stored
+      static_assert(kIdsPerLane * kEmitThreads == sizeof(st_ids) / sizeof(st_ids[0]), "idr covers st_ids");
+#pragma unroll
+      for (uint32_t j = 0; j < kIdsPerLane; ++j) idr[j] = st_ids[lid + j * kEmitThreads];
+      __syncthreads();  // every staged id is in registers
+      __asm__ volatile("" : "=v"(lid) : "0"(tid));
       uint64_t* sv = (uint64_t*)st_ids;  // 2 * kRecPerRegion u32 = kMaxS u64
       // (V = 5 keeps v[] live through the count pass rather than rereading S here: 5.86 vs
       // 5.98 ms per 2^27 dense round, profiles/r04_e/summary.txt)
 #pragma unroll
       for (uint32_t q = 0; q < kQ; ++q) sv[tid + q * kEmitThreads] = v[q];
       __syncthreads();
-      if constexpr (SHARD) {  // V = 6, 8: every value slot beside its u32 id (no holes)
-#pragma unroll 4
-        for (uint32_t e = tid; e < total; e += kEmitThreads)
-          rec_st(&gvals[e], sv[(gids[e] >> kTileDLog) & kIdNMask]);
-      } else {
-        uint32_t* gprec = b.prec + (size_t)s * g.rp * 3;
-#pragma unroll 4
-        for (uint32_t e = tid; e < total; e += kEmitThreads) {
-          const uint32_t id = split ? id_of_pair(gdst[e], gsrc[e]) : gids[e];
-          const uint64_t x = sv[(id >> kTileDLog) & kIdNMask];  // (one-shard big regions always pack: g.aos)
-          prec_st(&gprec[3 * e], (uint32_t)x, (uint32_t)(x >> 32), id);
+      uint32_t* gprec = SHARD ? nullptr : b.prec + (size_t)s * g.rp * 3;
+#pragma unroll
+      for (uint32_t j0 = 0; j0 < kIdsPerLane; j0 += kGroup) {
+        if (j0 * kEmitThreads >= total) break;  // (block-uniform)
+        uint64_t x[kGroup];
+#pragma unroll
+        for (uint32_t c = 0; c < kGroup; ++c) x[c] = sv[(idr[j0 + c] >> kTileDLog) & kIdNMask];
+#pragma unroll
+        for (uint32_t c = 0; c < kGroup; ++c) {
+          const uint32_t e = lid + (j0 + c) * kEmitThreads, id = idr[j0 + c];
+          if (e >= total) continue;
+          if constexpr (SHARD) {  // V = 6, 8: every value slot beside its u32 id (no holes)
+            rec_st(&gids[e], id);
+            rec_st(&gvals[e], x[c]);
+          } else {  // (one-shard big regions always pack: g.aos)
+            rec_st(&gdst[e], dst_of(id));
+            rec_st(&gsrc[e], src_of(id));
+            prec_st(&gprec[3 * e], (uint32_t)x[c], (uint32_t)(x[c] >> 32), id);
+          }
         }
+        // one group at a time: its value loads before its stores, the next group's after
+        __builtin_amdgcn_sched_barrier(0);
       }
     }
   } else
@@ -1044,9 +1069,12 @@ __global__ __launch_bounds__(kTileThreads) void bin_apply_kernel(BinGeom g, BinB
   __shared__ int32_t wlist[(kTileThreads / 64) * 64 * kPushRPL];
   const uint32_t tid = threadIdx.x;
   // persistent (grid apply_grid(nt_d)): virtual block v = blockIdx.x,
-  // +gridDim.x, ... applies tile xcd_remap(v, nt_d) (same XCD as blockIdx.x);
-  // the next tile's S_t loads into registers during the current tile's work.  In
-  // place stays safe: only this block reads or writes S[X] of its tiles.
+  // +gridDim.x, ... applies tile xcd_remap(v, nt_d) (same XCD as blockIdx.x).
+  // Each tile's S_t is loaded at the start of its own turn: loading the next
+  // tile's into registers during the current tile's work spilled (13 VGPRs at 2
+  // slots) and its A/B was within run-to-run noise, so it was left off
+  // (profiles/r01_experiments/apply_persistent/).  In place stays safe: only
+  // this block reads or writes S[X] of its tiles.
   const uint32_t nv = g.nt_d;
   // b.dyn (one shard): tiles from the per-XCD queues (TileQueue), else the static order
   const bool dyn = b.dyn && nv >= 8 && (nv & 7u) == 0;
