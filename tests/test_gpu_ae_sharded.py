@@ -27,6 +27,14 @@ CASES = [  # N, K, fanout, seed, fail, recover, G
     (4099, 64, 3, 3, 0.02, 0.2, 2),
     (777, 1, 1, 11, 0.0, 0.0, 2),
     (100, 8, 1, 5, 0.05, 0.3, 4),  # 64-node row blocks: shards of 64, 36, 0 and 0 nodes
+    # row widths L = 2, 4, 32 of the aex_* kernels (K = 2, 4, 32), and fanouts above 3: the churn word
+    # on its own Philox stream, requests of Philox blocks past the first (k = 5, 9)
+    (20011, 2, 2, 21, 0.03, 0.25, 3),
+    (20011, 4, 3, 22, 0.03, 0.25, 2),
+    (20011, 32, 1, 23, 0.03, 0.25, 4),
+    (4099, 17, 5, 24, 0.03, 0.25, 3),
+    (20011, 16, 4, 25, 0.03, 0.25, 2),
+    (130, 3, 9, 26, 0.05, 0.3, 4),  # shards of 64, 64, 2 and 0 nodes
 ]
 
 
