@@ -20,6 +20,7 @@
 #include "ae_sharded.h"
 #include "antientropy.h"
 #include "binned.h"
+#include "devmem.h"
 #include "frontier.h"
 #include "sharded.h"
 #include "round.h"
@@ -66,7 +67,7 @@ struct gossip_engine {
   // gossip_round_wall: whole library-driven sharded rounds by class (dense / sparse / ANTIENTROPY)
   double wall_ms[3] = {};
   uint64_t wall_n[3] = {}, wall_link[3] = {};
-  hipEvent_t wall_ev[2] = {};
+  DevEvent wall_ev[2];
 
   uint64_t N = 0, Nl = 0, lo = 0, hi = 0, nown = 0;
   uint32_t R = 0, W = 0, k = 0, mode = 0, G = 1, rank = 0;
@@ -77,50 +78,56 @@ struct gossip_engine {
   // Random modes: two gathered images [G][W][Nl]; S_t is this rank's slice of
   // img[cur], S_{t+1} its slice of img[cur^1], so the all-gather runs in place.
   // FLOOD: S/Snext/Sprev/skip are shard-sized and the frontier F is the slice of imgF.
-  uint64_t* img[2] = {nullptr, nullptr};
+  //
+  // Device memory, pinned memory and events are owned by the DevBuf / PinBuf / DevEvent members
+  // (devmem.h): deleting the engine frees them.  Raw pointers here and in the kernel-argument
+  // structs (fa, fw, bb, fb, lf, sb, sbb, xb, rbb) are views into them.
+  DevBuf<uint64_t> img[2];
   int cur = 0;
-  uint64_t* imgF = nullptr;
+  DevBuf<uint64_t> imgF;
+  DevBuf<uint64_t> flood_st[4];  // FLOOD: the shard-sized buffers that S, Snext, Sprev and skip rotate over
   uint64_t* S = nullptr;      // S_t, own shard [W][Nl]
   uint64_t* Snext = nullptr;  // S_{t+1}
   uint64_t* Sprev = nullptr;  // FLOOD S_{t-1}
   uint64_t* skip = nullptr;   // FLOOD sender-skip masks
   uint64_t* F = nullptr;      // FLOOD frontier (exchange send slice)
-  uint64_t* partial_d = nullptr;
-  uint64_t* partial_h = nullptr;  // pinned
-  uint64_t* scratch_d = nullptr;  // 8 B
-  uint32_t *orow = nullptr, *ocol = nullptr, *irow = nullptr, *icol = nullptr;
+  DevBuf<uint64_t> partial_d;
+  PinBuf<uint64_t> partial_h;
+  DevBuf<uint64_t> scratch_d;  // 8 B
+  DevBuf<uint32_t> orow, ocol, irow, icol;
   bool has_topo = false;
   // stall mode, random modes: streak per node, all N nodes on every shard
-  uint8_t* stall_d = nullptr;
+  DevBuf<uint8_t> stall_d;
   // FLOOD with faults, one shard: per out-edge pending values and first senders
   bool flood_edges = false;
   FloodWalks fw{nullptr, nullptr, nullptr, 0u};  // FLOOD with faults: the walks
+  DevBuf<uint32_t> fw_cur, fw_snd;
+  DevBuf<uint8_t> fw_att;
   // ANTIENTROPY: rows V[n*K + c], alive bytes, global max vector
-  uint32_t *V = nullptr, *Vn = nullptr, *target = nullptr;
-  uint64_t *alive = nullptr, *alive_n = nullptr;  // [chunks][2]: alive bits, stale bits (AeArgs::ab)
+  DevBuf<uint32_t> V, Vn, target;
+  DevBuf<uint64_t> alive, alive_n;  // [chunks][2]: alive bits, stale bits (AeArgs::ab)
   // ANTIENTROPY sparse rounds: stale bitmap of V, edge list + row snapshots,
   // fix-up claims; aux = [0] stale nodes [1] listed edges (device) / ae_aux_h (pinned host copy)
-  // (one-engine ANTIENTROPY: aux is the two words after partial_d / partial_h, so one copy and
-  // one memset per round move both)
+  // (aux is the two words after partial_d / partial_h, so one copy and one memset per round
+  // move both)
   uint64_t *ae_aux = nullptr, *ae_aux_h = nullptr;
-  bool ae_aux_alias = false;
   // one-engine ANTIENTROPY: gossip_reset's zeroing of V is pending (set_dev does it before any other
   // call; gossip_inject_random, which writes every row, drops it: a 4 GiB memset at configs[4])
   bool ae_v_zero = false;
-  uint32_t *ae_eid = nullptr, *ae_erow = nullptr, *ae_claim = nullptr, *ae_segn = nullptr;
-  void* ae_pmask = nullptr;  // dense rounds: [N][k] push masks
+  DevBuf<uint32_t> ae_eid, ae_erow, ae_claim, ae_segn;
+  DevBuf<uint8_t> ae_pmask;  // dense rounds: [N][k] push masks
   uint32_t ae_nseg = 1, ae_spc = 1, ae_segcap = 1;
   bool ae_bin = false;  // binned sparse scan (AeArgs::brec)
   AeBinGeom ae_bg{};
-  uint32_t* ae_brec = nullptr;
-  uint16_t* ae_boff = nullptr;
+  DevBuf<uint32_t> ae_brec;
+  DevBuf<uint16_t> ae_boff;
   // binned dense rounds: run starts per region over 2^14-node tiles;
   // ae_dbin = the engine's geometry fits, ae_dbin_on = gossip_set_param "ae_dense_bin"
   bool ae_dbin = false, ae_dbin_on = true;
   uint32_t ae_dcap = 0;  // gossip_set_param "ae_dense_cap" (tests: ranges, overflow fallback)
   bool ae_dfilt = true;  // "ae_dense_filter": binned dense rounds skip exchanges that move no row (kAeSbValid)
   AeBinGeom ae_dg{};
-  uint16_t* ae_dboff = nullptr;
+  DevBuf<uint16_t> ae_dboff;
   uint64_t ae_dense_fallbacks = 0;
   uint64_t ae_cap = 0, ae_hash = 0, ae_stale = 0, ae_alive = 0, ae_full = 0;
   uint32_t ae_epoch = 0;
@@ -132,22 +139,23 @@ struct gossip_engine {
   // predecessor; per round a slot of totals + aux and a gate word
   uint32_t ae_ahead = 8;
   bool ae_dense_next = false;    // the next round runs dense (a pipelined sparse round overflowed)
-  uint64_t *ae_slot_d = nullptr, *ae_slot_h = nullptr;
-  uint32_t* ae_gate_d = nullptr;
+  DevBuf<uint64_t> ae_slot_d;
+  PinBuf<uint64_t> ae_slot_h;
+  DevBuf<uint32_t> ae_gate_d;
   // sharded ANTIENTROPY (G > 1): V/Vn = own rows [Nl][K], aex_img = every
   // shard's {alive, stale} word pairs (the all-gather image, ae_sharded.h AexArgs::img)
   bool aex = false;
   bool aex_target_ok = false;
   uint32_t aex_rw = 0, aex_pw = 0;
-  uint64_t *aex_img = nullptr, *aex_cnt = nullptr, *aex_boff = nullptr, *aex_cnt_h = nullptr;
+  DevBuf<uint64_t> aex_img, aex_cnt, aex_boff;
+  PinBuf<uint64_t> aex_cnt_h;
   uint64_t aex_churned = ~0ull;  // the round whose churn the own alive words hold
-  uint32_t *aex_bcnt = nullptr, *aex_req = nullptr, *aex_loc = nullptr, *aex_in = nullptr, *aex_resp_out = nullptr,
-           *aex_resp_in = nullptr, *aex_tmp = nullptr;
-  uint64_t aex_req_cap = 0, aex_in_cap = 0, aex_out_cap = 0, aex_nin = 0, aex_nreq = 0, aex_nloc = 0;
+  DevBuf<uint32_t> aex_bcnt, aex_req, aex_loc, aex_in, aex_resp_out, aex_resp_in, aex_tmp;
+  uint64_t aex_nin = 0, aex_nreq = 0, aex_nloc = 0;
   // Vn seeding (launch_aex_seed_next): after a completed round Vn holds S_{t-1} and aex_dirty marks the
   // rows that round raised, so the next round copies only those; any direct write (reset, inject) voids it
-  uint64_t* aex_dirty = nullptr;  // [ceil(Nl / 64)]
-  uint8_t* aex_verdict = nullptr;  // [nown] the count pass's listed exchanges per own node
+  DevBuf<uint64_t> aex_dirty;   // [ceil(Nl / 64)]
+  DevBuf<uint8_t> aex_verdict;  // [nown] the count pass's listed exchanges per own node
   bool aex_patch_ok = false, aex_round_done = false;
   bool aex_track = false;  // this round marks the rows it raises (few items: ae_request_recv decides)
   // incremental stats (launch_aex_finish inc): the own stale words and hash part of S_t are exact
@@ -158,7 +166,7 @@ struct gossip_engine {
   BinGeom bg{};
   BinBufs bb{};
   uint32_t* bb_dyn = nullptr;  // the tile queues (gossip_set_param "tile_queues" 0 clears bb.dyn)
-  void* bin_mem = nullptr;
+  DevBuf<uint8_t> bin_mem;
   // placement of the record slab (place_bins): the dense round's time depends on where the slab
   // lands (4.98-5.48 ms at 2^27 across fresh allocations in one process, profiles/r05_pl/r05_pl4/,
   // r05_pl6/); before the first round place_tries allocations are timed on a zero-state trial round
@@ -171,7 +179,7 @@ struct gossip_engine {
   // frontier (sparse-round) path, on top of the binned one
   bool frontier = false;
   FrontierBufs fb{};
-  void* fr_mem = nullptr;
+  DevBuf<uint8_t> fr_mem;
   bool fr_valid = false;          // partial_d holds the totals of S and the bitmaps are exact
   double sparse_frac = 1.0 / 16;  // rare fraction at or below which a round runs sparse (sparse_frac_of)
   bool sparse_frac_set = false;   // set by gossip_set_param (else the sharded defaults apply)
@@ -187,8 +195,8 @@ struct gossip_engine {
   // pipelined rounds (binned engines): the host picks each round's path from the
   // totals it has read, predicted forward over the rounds still in flight, and
   // stays up to `ahead` rounds in front
-  uint64_t* ring_h = nullptr;  // [kRing][part_len + 1] host-mapped totals + sequence word per round
-  uint64_t* ring_d = nullptr;
+  PinBuf<uint64_t> ring_h;     // [kRing][part_len + 1] host-mapped totals + sequence word per round
+  uint64_t* ring_d = nullptr;  // its device address
   uint64_t seq = 0;
   uint32_t ahead = 2;
   // sharded sparse rounds (G > 1, W == 1 random modes; sharded.h):
@@ -202,30 +210,30 @@ struct gossip_engine {
   SxGeom sg{};
   SxBufs sb{};
   FrontierBufs lf{};
-  void *lf_mem = nullptr, *sx_mem = nullptr;
-  SxItem* rare_recv = nullptr;
+  DevBuf<uint8_t> lf_mem, sx_mem;
+  DevBuf<SxItem> rare_recv;
   // sharded dense rounds on the binned pipeline (binned.h: SbGeom), else the direct kernels
   bool sbin = false;
   SbGeom sbg{};
   SbBufs sbb{};
-  void* sb_mem = nullptr;
+  DevBuf<uint8_t> sb_mem;
   bool sb_pre = false;  // gossip_dense_prepare ran for this round
-  hipEvent_t ev_pre[2] = {};
+  DevEvent ev_pre[2];
   bool ev_pre_pending = false;
-  SxItem* msg_recv = nullptr;
-  uint64_t rare_recv_cap = 0, msg_recv_cap = 0, sx_stride = 0;
+  DevBuf<SxItem> msg_recv;
+  uint64_t sx_stride = 0;
   // exchange dense rounds (binned.h: XdGeom), buffers allocated at the first one
   bool xd = false, xd_planned = false;
   uint32_t xd_shards = 6;  // gossip_set_param "xd_shards": G at which dense rounds become exchange rounds
   XdGeom xg{};
   XdBufs xb{};
-  void *xd_smem = nullptr, *xd_rmem = nullptr;
-  uint64_t xd_rcap = 0, xd_nin = 0;
-  uint32_t* xd_cnt_h = nullptr;  // pinned [G]
+  DevBuf<uint8_t> xd_smem, xd_rmem;
+  uint64_t xd_rcap = 0, xd_nin = 0;  // xd_rcap: the items xd_rmem was carved for (xd_carve_recv)
+  PinBuf<uint32_t> xd_cnt_h;  // [G]
   uint32_t xd_filt = 0;          // this round's edge filter (dense_filter of the global totals)
   bool xd_cls_ok = false;        // gossip_xd_classes handed out the own bitmaps for this round
-  uint64_t* xd_cls = nullptr;    // [G][2 * nwl] every shard's occupancy bitmaps of S_t (all-gather in place)
-  uint8_t* xd_keep = nullptr;    // [nown] per sender: the edges that survive the filter (count pass -> emit)
+  DevBuf<uint64_t> xd_cls;       // [G][2 * nwl] every shard's occupancy bitmaps of S_t (all-gather in place)
+  DevBuf<uint8_t> xd_keep;       // [nown] per sender: the edges that survive the filter (count pass -> emit)
   // class-coded state exchange for dense image rounds (sharded.h cc_*), plan kind 4
   bool cc_planned = false;
   double cc_frac = 0.75;
@@ -237,8 +245,8 @@ struct gossip_engine {
   bool rep_img_ok = false;      // the image holds S_t of every node (the last round was replicated)
   BinGeom rbg{};
   BinBufs rbb{};
-  void* rep_mem = nullptr;      // the one-GPU record slab over all N nodes, at the first replicated round
-  uint64_t* rep_part = nullptr; // that round's whole-image totals (scratch: the ranks report own-slice totals)
+  DevBuf<uint8_t> rep_mem;      // the one-GPU record slab over all N nodes, at the first replicated round
+  DevBuf<uint64_t> rep_part;    // that round's whole-image totals (scratch: the ranks report own-slice totals)
   // gossip_set_param "link_gbps": sharded random-mode rounds pick sparse / dense by a per-rank
   // cost model with a link term (shard_round_costs); 0 = the fixed sparse_frac thresholds
   double link_gbps = 76.0;
@@ -246,19 +254,19 @@ struct gossip_engine {
   double model_ms = 0, model_link_ms = 0;  // the modelled per-rank ms of the planned rounds since reset_timing
   uint64_t model_rounds = 0;
   double plan_cost[2] = {};  // the last plan's modelled sparse / dense ms (tools/shard_probe.py)  // gossip_set_param "cc_frac": at most this global fraction of mixed nodes
-  uint64_t* cc_bits = nullptr;  // [G][cc_slot_words] every shard's bitmaps + prefix (all-gather in place)
-  uint64_t* cc_vals = nullptr;  // [G][stride] the shards' mixed words
-  uint64_t cc_vals_cap = 0, cc_stride = 0;
-  uint64_t* sx_host = nullptr;  // pinned: [G + 2] counts / list bases
-  uint64_t* pub_d = nullptr;    // device values for device-side collectives (gossip_*_dev): [G] counts, [1] count, partials
+  DevBuf<uint64_t> cc_bits;     // [G][cc_slot_words] every shard's bitmaps + prefix (all-gather in place)
+  DevBuf<uint64_t> cc_vals;     // [G][stride] the shards' mixed words
+  uint64_t cc_stride = 0;
+  PinBuf<uint64_t> sx_host;     // [G + 2] counts / list bases
+  DevBuf<uint64_t> pub_d;       // device values for device-side collectives (gossip_*_dev): [G] counts, [1] count, partials
 
-  hipEvent_t ev[kTimers][2] = {};
+  DevEvent ev[kTimers][2];
   double time_ms[kTimers] = {};
   uint64_t launches[kTimers] = {};
   bool timing = false;
   bool ev_pending[kTimers] = {};
   // per-round events of the pipelined rounds (timers 3 and 4), one pair per ring slot
-  hipEvent_t evr[kRing][2] = {};
+  DevEvent evr[kRing][2];
   int64_t evr_round[kRing] = {-1, -1, -1, -1, -1, -1, -1, -1};
   int evr_kind[kRing] = {};
 
@@ -270,6 +278,10 @@ struct gossip_engine {
     va_end(ap);
     err = buf;
     return code;
+  }
+  // (the buffers and events free themselves; a borrowed stream, gossip_set_stream, stays the caller's)
+  ~gossip_engine() {
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 };
 
@@ -292,58 +304,6 @@ int set_dev(gossip_engine* e) {
 
 // stats vector: [0] full [1] alive [2] messages [3] hash [4, 4+R) infected, [4+R] nonzero nodes (internal)
 size_t part_len(const gossip_engine* e) { return 5 + (size_t)e->R; }
-
-void free_all(gossip_engine* e) {
-  uint64_t* bufs[] = {e->img[0], e->img[1], e->imgF, e->partial_d, e->scratch_d};
-  if (e->mode == GOSSIP_MODE_FLOOD) {
-    uint64_t* fb[] = {e->S, e->Snext, e->Sprev, e->skip};
-    for (uint64_t* b : fb)
-      if (b) (void)hipFree(b);
-  }
-  for (uint64_t* b : bufs)
-    if (b) (void)hipFree(b);
-  uint32_t* tb[] = {e->orow, e->ocol, e->irow, e->icol, e->fw.cur, e->fw.snd};
-  for (uint32_t* b : tb)
-    if (b) (void)hipFree(b);
-  void* fe[] = {e->stall_d, e->fw.att};
-  for (void* b : fe)
-    if (b) (void)hipFree(b);
-  if (e->bin_mem) (void)hipFree(e->bin_mem);
-  if (e->rep_mem) (void)hipFree(e->rep_mem);
-  if (e->rep_part) (void)hipFree(e->rep_part);
-  if (e->fr_mem) (void)hipFree(e->fr_mem);
-  void* sx[] = {e->lf_mem, e->sx_mem, e->rare_recv, e->msg_recv, e->sb_mem, e->xd_smem, e->xd_rmem,
-                e->cc_bits, e->cc_vals, e->xd_cls, e->xd_keep};
-  if (e->xd_cnt_h) (void)hipHostFree(e->xd_cnt_h);
-  for (void* b : sx)
-    if (b) (void)hipFree(b);
-  if (e->sx_host) (void)hipHostFree(e->sx_host);
-  if (e->pub_d) (void)hipFree(e->pub_d);
-  if (e->ae_aux_alias) e->ae_aux = e->ae_aux_h = nullptr;  // inside partial_d / partial_h
-  void* ae[] = {e->V, e->Vn, e->target, e->alive, e->alive_n, e->ae_aux, e->ae_claim, e->ae_eid, e->ae_erow, e->ae_segn, e->ae_pmask,
-                e->ae_brec, e->ae_boff, e->ae_dboff, e->aex_img, e->aex_cnt, e->aex_boff, e->aex_bcnt, e->aex_req, e->aex_loc,
-                e->aex_in, e->aex_resp_out, e->aex_resp_in, e->aex_tmp, e->aex_dirty, e->aex_verdict};
-  if (e->aex_cnt_h) (void)hipHostFree(e->aex_cnt_h);
-  for (void* b : ae)
-    if (b) (void)hipFree(b);
-  if (e->partial_h) (void)hipHostFree(e->partial_h);
-  if (e->ae_aux_h) (void)hipHostFree(e->ae_aux_h);
-  if (e->ae_slot_d) (void)hipFree(e->ae_slot_d);
-  if (e->ae_gate_d) (void)hipFree(e->ae_gate_d);
-  if (e->ae_slot_h) (void)hipHostFree(e->ae_slot_h);
-  if (e->ring_h) (void)hipHostFree(e->ring_h);
-  for (auto& p : e->ev)
-    for (auto& x : p)
-      if (x) (void)hipEventDestroy(x);
-  for (auto& x : e->ev_pre)
-    if (x) (void)hipEventDestroy(x);
-  for (auto& x : e->wall_ev)
-    if (x) (void)hipEventDestroy(x);
-  for (auto& p : e->evr)
-    for (auto& x : p)
-      if (x) (void)hipEventDestroy(x);
-  if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
-}
 
 RoundArgs make_args(gossip_engine* e, const uint64_t* gathered) {
   RoundArgs a{};
@@ -491,9 +451,9 @@ AeArgs make_ae_args(gossip_engine* e) {
 // Device time (ms) per launch of `run` on the engine's stream: the average of two after a warm-up.
 template <class Run>
 int timed_trial(gossip_engine* e, Run run, float* ms) {
-  hipEvent_t ev[2];
-  HIP_OK(e, hipEventCreate(&ev[0]));
-  HIP_OK(e, hipEventCreate(&ev[1]));
+  DevEvent ev[2];
+  HIP_OK(e, ev[0].create());
+  HIP_OK(e, ev[1].create());
   bool ok = true;
   for (int i = 0; i < 3 && ok; ++i) {
     if (i == 1) ok = hipEventRecord(ev[0], e->stream) == hipSuccess;
@@ -502,19 +462,18 @@ int timed_trial(gossip_engine* e, Run run, float* ms) {
   ok = ok && hipEventRecord(ev[1], e->stream) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
        hipEventElapsedTime(ms, ev[0], ev[1]) == hipSuccess;
   *ms *= 0.5f;
-  (void)hipEventDestroy(ev[0]);
-  (void)hipEventDestroy(ev[1]);
   return ok ? GOSSIP_OK : e->fail(GOSSIP_EHIP, "placement trial round failed");
 }
 
 // Placement of a slab: `trial(slab, &ms)` times a round over the slab at `slab`;
-// up to place_tries allocations of `bytes` are tried and the fastest is kept in *mem.  At most two
+// up to place_tries allocations of `bytes` are tried and the fastest is kept in mem.  At most two
 // slabs are held beside the kept one: the best so far, the last loser (held while the next
 // candidate is allocated, so that candidate cannot reuse its pages) and the new candidate
-// (round 5 held every candidate: 75 GB at 2^27).  Timer 5 gets the trial rounds.  Returns whether
-// *mem moved.
+// (round 5 held every candidate: 75 GB at 2^27).  Timer 5 gets the trial rounds.  `mem` owns the
+// best slab throughout (a faster candidate is swapped in), `held` the last loser.  Returns whether
+// mem moved.
 template <class Trial>
-int place_slab(gossip_engine* e, void** mem, size_t bytes, Trial trial, bool* moved, const char* what) {
+int place_slab(gossip_engine* e, DevBuf<uint8_t>& mem, size_t bytes, Trial trial, bool* moved, const char* what) {
   *moved = false;
   // A wall-time budget: on some boxes and processes a fresh multi-GiB hipMalloc / hipFree takes
   // 0.1 s to seconds instead of milliseconds (a 3.3 s first step at 2^27 where 130 ms is usual,
@@ -523,59 +482,52 @@ int place_slab(gossip_engine* e, void** mem, size_t bytes, Trial trial, bool* mo
   // left 2 of 4 engines in the 5.5-ms mode, profiles/r06_vmm/budget400)
   constexpr double kPlaceBudgetMs = 2000.0;
   const auto t_start = std::chrono::steady_clock::now();
-  void* best = *mem;
-  void* held = nullptr;
+  const void* first = mem.get();
+  DevBuf<uint8_t> held;
   float best_ms = 0.f;
-  int rc = trial(best, &best_ms);
+  int rc = trial(mem.get(), &best_ms);
   auto account = [&](float ms) {
     e->time_ms[5] += 3.0 * ms;
     e->launches[5] += 3;
   };
   account(best_ms);
 #ifdef GOSSIP_EXP_PLACE_LOG
-  std::fprintf(stderr, "%s: candidate 0 slab %p trial %.1f us\n", what, best, best_ms * 1e3);
+  std::fprintf(stderr, "%s: candidate 0 slab %p trial %.1f us\n", what, (void*)mem.get(), best_ms * 1e3);
 #endif
   for (uint32_t i = 1; i < e->place_tries && rc == GOSSIP_OK; ++i) {
     if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count() > kPlaceBudgetMs)
       break;
-    void* p = nullptr;
+    DevBuf<uint8_t> p;
 #ifdef GOSSIP_EXP_PLACE_LOG
     const auto t0 = std::chrono::steady_clock::now();
 #endif
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-      (void)hipGetLastError();  // no room for another trial: keep the best so far
-      break;
-    }
+    if (p.alloc(bytes, false) != hipSuccess) break;  // no room for another trial: keep the best so far
 #ifdef GOSSIP_EXP_PLACE_LOG
     const auto t1 = std::chrono::steady_clock::now();
 #endif
     float ms = 0.f;
-    rc = trial(p, &ms);
+    rc = trial(p.get(), &ms);
     account(ms);
 #ifdef GOSSIP_EXP_PLACE_LOG
-    std::fprintf(stderr, "%s: candidate %u slab %p trial %.1f us, hipMalloc %.1f ms\n", what, i, p, ms * 1e3,
+    std::fprintf(stderr, "%s: candidate %u slab %p trial %.1f us, hipMalloc %.1f ms\n", what, i, (void*)p.get(), ms * 1e3,
                  std::chrono::duration<double, std::milli>(t1 - t0).count());
 #endif
-    void* loser = p;
-    if (rc == GOSSIP_OK && ms < best_ms) {
-      loser = best;
-      best = p;
+    if (rc == GOSSIP_OK && ms < best_ms) {  // p takes the loser
+      mem.swap(p);
       best_ms = ms;
     }
 #ifdef GOSSIP_EXP_PLACE_LOG
     const auto t2 = std::chrono::steady_clock::now();
 #endif
-    if (held) (void)hipFree(held);  // (its trial has completed: timed_trial synchronizes)
+    (void)held.reset();  // (its trial has completed: timed_trial synchronizes)
 #ifdef GOSSIP_EXP_PLACE_LOG
-    std::fprintf(stderr, "%s: hipFree %.1f ms\n", what,
+    std::fprintf(stderr, "%s: free %.1f ms\n", what,
                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count());
 #endif
-    held = loser;
+    held = std::move(p);
   }
   (void)what;
-  if (held) (void)hipFree(held);
-  *moved = best != *mem;
-  *mem = best;
+  *moved = mem.get() != first;
   return rc;
 }
 
@@ -623,13 +575,12 @@ int place_bins(gossip_engine* e) {
     return GOSSIP_OK;
   };
   if (!e->binned || e->place_tries <= 1 || bytes < (512ull << 20) || !e->img[1]) return GOSSIP_OK;
-  uint64_t* part = nullptr;
-  HIP_OK(e, hipMalloc((void**)&part, (part_len(e) + 8) * 8));
+  DevBuf<uint64_t> part;
+  HIP_OK(e, part.alloc(part_len(e) + 8, false));
   bool moved = false;
-  const int rc = place_slab(e, &e->bin_mem, bytes, [&](void* slab, float* ms) {
+  const int rc = place_slab(e, e->bin_mem, bytes, [&](void* slab, float* ms) {
     return serve_trial(e, e->bg, e->bb.dyn != nullptr, slab, e->img[1], part, ms);
   }, &moved, "place_bins");
-  (void)hipFree(part);
   if (moved) {
     const int r2 = recarve();
     return rc != GOSSIP_OK ? rc : r2;
@@ -645,15 +596,13 @@ int place_sb(gossip_engine* e) {
   e->sb_placed = true;
   const size_t bytes = sb_bytes(e->sbg);
   if (!e->sbin || e->place_tries <= 1 || bytes < (512ull << 20)) return GOSSIP_OK;
-  uint64_t *part = nullptr, *snext = nullptr;
-  HIP_OK(e, hipMalloc((void**)&part, (part_len(e) + 8) * 8));
-  if (hipMalloc((void**)&snext, std::max<uint64_t>(e->nown, 1) * 8) != hipSuccess) {
-    (void)hipFree(part);
+  DevBuf<uint64_t> part, snext;
+  HIP_OK(e, part.alloc(part_len(e) + 8, false));
+  if (snext.alloc(std::max<uint64_t>(e->nown, 1), false) != hipSuccess)
     return e->fail(GOSSIP_ENOMEM, "placement scratch allocation failed");
-  }
   bool moved = false;
   const uint64_t* image = current_image(e);
-  const int rc = place_slab(e, &e->sb_mem, bytes, [&](void* slab, float* ms) {
+  const int rc = place_slab(e, e->sb_mem, bytes, [&](void* slab, float* ms) {
     SbBufs b{};
     sb_carve(e->sbg, slab, &b);
     return timed_trial(e, [&] {
@@ -662,9 +611,7 @@ int place_sb(gossip_engine* e) {
                              nullptr, nullptr, e->stream);
     }, ms);
   }, &moved, "place_sb");
-  (void)hipStreamSynchronize(e->stream);
-  (void)hipFree(part);
-  (void)hipFree(snext);
+  (void)hipStreamSynchronize(e->stream);  // (before the scratch goes)
   if (moved) sb_carve(e->sbg, e->sb_mem, &e->sbb);
   return rc;
 }
@@ -940,7 +887,7 @@ int wait_slot(gossip_engine* e, uint32_t slot, uint64_t want) {
 int read_totals(gossip_engine* e, std::vector<uint64_t>* out) {
   HIP_OK(e, hipMemcpyAsync(e->partial_h, e->partial_d, part_len(e) * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(e, hipStreamSynchronize(e->stream));
-  out->assign(e->partial_h, e->partial_h + part_len(e));
+  out->assign(e->partial_h.get(), e->partial_h + part_len(e));
   return GOSSIP_OK;
 }
 
@@ -1045,40 +992,32 @@ int ae_place(gossip_engine* e) {
   const size_t vb = (size_t)e->N * e->R * 4;
   if (e->place_tries <= 1 || !(e->ae_dbin && e->ae_dbin_on) || vb < (512ull << 20)) return GOSSIP_OK;
   const size_t pl = part_len(e);
-  uint64_t* part = nullptr;
-  HIP_OK(e, hipMalloc((void**)&part, (pl + 8) * 8));
+  DevBuf<uint64_t> part;
+  HIP_OK(e, part.alloc(pl + 8, false));
   struct Cand {
-    uint32_t *V, *Vn;
+    DevBuf<uint32_t> V, Vn;
   };
   // (as place_slab: the kept rows, the best candidate so far, the last loser held while the next
   // candidate is allocated, and that candidate: at most two sets of rows beside the kept ones)
-  Cand best{e->V, e->Vn}, held{nullptr, nullptr};
+  // The engine's V / Vn own the best rows throughout: a faster candidate is swapped in.
+  Cand held;
   float best_ms = 0.f;
-  hipEvent_t ev[2];
-  HIP_OK(e, hipEventCreate(&ev[0]));
-  HIP_OK(e, hipEventCreate(&ev[1]));
+  DevEvent ev[2];
+  HIP_OK(e, ev[0].create());
+  HIP_OK(e, ev[1].create());
   int rc = GOSSIP_OK;
-  auto release = [](Cand& c) {
-    if (c.V) (void)hipFree(c.V);
-    if (c.Vn) (void)hipFree(c.Vn);
-    c = Cand{nullptr, nullptr};
-  };
   const uint32_t tries = e->place_tries;  // 12 by default: a fast placement of the rows is ~1 in 8
   for (uint32_t i = 0; i < tries && rc == GOSSIP_OK; ++i) {
-    Cand c = best;
+    Cand c;  // (candidate 0: the engine's own rows)
     if (i > 0) {
       // the rows carry the mode, the records do not (profiles/r05_pl/r05_aem/): only the rows move
-      c = Cand{nullptr, nullptr};
-      if (hipMalloc((void**)&c.V, vb) != hipSuccess || hipMalloc((void**)&c.Vn, vb) != hipSuccess) {
-        (void)hipGetLastError();  // no room for another trial: keep the best so far
-        release(c);
-        break;
-      }
-      if (hipMemcpyAsync(c.V, best.V, vb, hipMemcpyDeviceToDevice, e->stream) != hipSuccess) rc = GOSSIP_EHIP;
+      if (c.V.alloc(vb / 4, false) != hipSuccess || c.Vn.alloc(vb / 4, false) != hipSuccess)
+        break;  // no room for another trial: keep the best so far
+      if (hipMemcpyAsync(c.V, e->V, vb, hipMemcpyDeviceToDevice, e->stream) != hipSuccess) rc = GOSSIP_EHIP;
     }
     AeArgs d = make_ae_args(e);
-    d.V = c.V;
-    d.Vn = c.Vn;
+    d.V = i ? c.V.get() : e->V.get();
+    d.Vn = i ? c.Vn.get() : e->Vn.get();
     d.partial = part;
     d.aux = part + pl;
     d.zero = part;
@@ -1105,23 +1044,15 @@ int ae_place(gossip_engine* e) {
       best_ms = ms;
       continue;
     }
-    Cand loser = c;
-    if (rc == GOSSIP_OK && ms < best_ms) {
-      loser = best;
-      best = c;
+    if (rc == GOSSIP_OK && ms < best_ms) {  // (a candidate's V holds a copy of the rows); c takes the loser
+      e->V.swap(c.V);
+      e->Vn.swap(c.Vn);
       best_ms = ms;
     }
     if (held.V) (void)hipStreamSynchronize(e->stream);  // (no trial is still reading the rows freed next)
-    release(held);
-    held = loser;
+    held = std::move(c);
   }
-  (void)hipEventDestroy(ev[0]);
-  (void)hipEventDestroy(ev[1]);
-  (void)hipFree(part);
-  HIP_OK(e, hipStreamSynchronize(e->stream));
-  release(held);
-  e->V = best.V;  // (a candidate's V holds a copy of the rows)
-  e->Vn = best.Vn;
+  HIP_OK(e, hipStreamSynchronize(e->stream));  // (before held and the scratch go)
   if (rc != GOSSIP_OK) return e->fail(rc, "ANTIENTROPY placement trial failed");
   return GOSSIP_OK;
 }
@@ -1227,9 +1158,9 @@ int step_ae(gossip_engine* e, uint32_t max_rounds, gossip_round_stats_t* stats, 
             uint32_t* rounds_done) {
   const size_t pl = part_len(e), sw = pl + 2;  // a slot: the totals, then aux[0..1]
   if (!e->ae_slot_d) {
-    HIP_OK(e, hipMalloc((void**)&e->ae_slot_d, kRing * sw * 8));
-    HIP_OK(e, hipMalloc((void**)&e->ae_gate_d, kRing * 4));
-    HIP_OK(e, hipHostMalloc((void**)&e->ae_slot_h, kRing * sw * 8, hipHostMallocDefault));
+    HIP_OK(e, e->ae_slot_d.alloc(kRing * sw, false));
+    HIP_OK(e, e->ae_gate_d.alloc(kRing, false));
+    HIP_OK(e, e->ae_slot_h.alloc(kRing * sw));
   }
   std::vector<uint64_t> part(pl);
   uint32_t r = 0;
@@ -1322,24 +1253,21 @@ int step_ae(gossip_engine* e, uint32_t max_rounds, gossip_round_stats_t* stats, 
 // own slice (and rebuilds its own bitmaps) like any other sharded round, so the driver's
 // all-reduce stays as it is.  Bits as the sharded kinds: the same draws and edges (§2).
 int rep_compute(gossip_engine* e) {
-  if (!e->rep_part) HIP_OK(e, hipMalloc((void**)&e->rep_part, (part_len(e) + 8) * 8));
+  if (!e->rep_part) HIP_OK(e, e->rep_part.alloc(part_len(e) + 8, false));
   if (!e->rep_mem) {
     e->rbg = make_bin_geom(e->N, e->k, (e->N + kTileD - 1) / kTileD > kBigFromTiles);
     const size_t bytes = bin_bytes(e->rbg);
-    if (hipMalloc(&e->rep_mem, bytes) != hipSuccess) {
-      e->rep_mem = nullptr;
+    if (e->rep_mem.alloc(bytes, false) != hipSuccess)
       return e->fail(GOSSIP_ENOMEM, "hipMalloc of %zu bytes (replicated-round records) failed", bytes);
-    }
     const bool dyn = e->rbg.nt_d >= 4096;  // (the tile queues pay past 4096 tiles, as on one GPU)
     // placed as the one-GPU slab (place_bins): the trials read the image, write only records
     if (e->place_tries > 1 && bytes >= (512ull << 20)) {
       bool moved = false;
-      if (int rc = place_slab(e, &e->rep_mem, bytes, [&](void* slab, float* ms) {
+      if (int rc = place_slab(e, e->rep_mem, bytes, [&](void* slab, float* ms) {
             return serve_trial(e, e->rbg, dyn, slab, current_image(e), e->rep_part, ms);
           }, &moved, "place_rep")) {
         (void)hipStreamSynchronize(e->stream);
-        (void)hipFree(e->rep_mem);  // (never carved: the next replicated round allocates again)
-        e->rep_mem = nullptr;
+        (void)e->rep_mem.reset();  // (never carved: the next replicated round allocates again)
         return rc;
       }
     }
@@ -1423,8 +1351,8 @@ int compute_round(gossip_engine* e, const uint64_t* gathered) {
 
 void rotate(gossip_engine* e) {
   if (e->mode == GOSSIP_MODE_ANTIENTROPY) {
-    if (!e->ae_sparse_last) std::swap(e->V, e->Vn);  // sparse rounds merge in place
-    std::swap(e->alive, e->alive_n);
+    if (!e->ae_sparse_last) e->V.swap(e->Vn);  // sparse rounds merge in place
+    e->alive.swap(e->alive_n);
   } else if (e->mode == GOSSIP_MODE_FLOOD) {
     uint64_t* tmp = e->Sprev;
     e->Sprev = e->S;
@@ -1495,14 +1423,10 @@ int ae_alloc_lists(gossip_engine* e, uint64_t cap_req) {
     e->ae_segcap = (cap >= kn && !forced) ? e->k * e->ae_spc * 64 : (uint32_t)((cap + e->ae_nseg - 1) / e->ae_nseg);
     e->ae_cap = (uint64_t)e->ae_segcap * e->ae_nseg;
   }
-  void* old[] = {e->ae_segn, e->ae_eid, e->ae_erow};
-  for (void* p : old)
-    if (p) HIP_OK(e, hipFree(p));
-  e->ae_segn = e->ae_eid = e->ae_erow = nullptr;
+  for (DevBuf<uint32_t>* b : {&e->ae_segn, &e->ae_eid, &e->ae_erow}) HIP_OK(e, b->reset());
   const size_t seg_edges = (size_t)e->ae_segcap * e->ae_nseg;
-  if (hipMalloc((void**)&e->ae_segn, (size_t)e->ae_nseg * 4) != hipSuccess ||
-      hipMalloc((void**)&e->ae_eid, seg_edges * 8) != hipSuccess ||
-      hipMalloc((void**)&e->ae_erow, seg_edges * 8 * e->R) != hipSuccess)
+  if (e->ae_segn.alloc(e->ae_nseg, false) != hipSuccess || e->ae_eid.alloc(seg_edges * 2, false) != hipSuccess ||
+      e->ae_erow.alloc(seg_edges * 2 * e->R, false) != hipSuccess)
     return e->fail(GOSSIP_ENOMEM, "hipMalloc of the ANTIENTROPY edge lists (%llu edges) failed",
                    (unsigned long long)seg_edges);
   HIP_OK(e, hipMemset(e->ae_segn, 0, (size_t)e->ae_nseg * 4));
@@ -1616,7 +1540,6 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
 
   auto bail = [&](int rc) {
     g_create_error = e->err;
-    free_all(e);
     delete e;
     return rc;
   };
@@ -1631,16 +1554,15 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
   e->own_stream = true;
   const size_t shard = (size_t)e->W * e->Nl * 8;
   const size_t image = shard * G;
-  auto alloc = [&](uint64_t** p, size_t bytes) {
-    if (hipMalloc((void**)p, bytes) != hipSuccess) {
-      e->err = "hipMalloc of " + std::to_string(bytes) + " bytes failed";
-      return false;
-    }
-    return hipMemset(*p, 0, bytes) == hipSuccess;
+  // `count` zeroed elements; the message names a failed hipMalloc (a failed memset leaves err as it is)
+  auto alloc = [&](auto& buf, size_t count) {
+    const hipError_t rc = buf.alloc(count, true);
+    if (rc != hipSuccess && !buf) e->err = "hipMalloc of " + std::to_string(count * sizeof(*buf.get())) + " bytes failed";
+    return rc == hipSuccess;
   };
-  if (!alloc(&e->partial_d, part_len(e) * 8 + 64) || !alloc(&e->scratch_d, 8)) return bail(GOSSIP_ENOMEM);
+  if (!alloc(e->partial_d, part_len(e) + 8) || !alloc(e->scratch_d, 1)) return bail(GOSSIP_ENOMEM);
   if (cfg->stall_rounds && e->mode >= GOSSIP_MODE_PUSH && e->mode <= GOSSIP_MODE_PUSHPULL) {
-    if (hipMalloc((void**)&e->stall_d, e->N) != hipSuccess || hipMemset(e->stall_d, 0, e->N) != hipSuccess) {
+    if (e->stall_d.alloc(e->N, true) != hipSuccess) {
       e->err = "hipMalloc of the stall streaks failed";
       return bail(GOSSIP_ENOMEM);
     }
@@ -1649,68 +1571,63 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
   }
   if (e->flood_edges) {  // one walk per (value, node); none running until a value is injected or learned
     const size_t nw = (size_t)e->R * e->N;
-    if (hipMalloc((void**)&e->fw.cur, nw * 4) != hipSuccess || hipMalloc((void**)&e->fw.snd, nw * 4) != hipSuccess ||
-        hipMalloc((void**)&e->fw.att, nw) != hipSuccess || hipMemset(e->fw.cur, 0xFF, nw * 4) != hipSuccess ||
-        hipMemset(e->fw.snd, 0xFF, nw * 4) != hipSuccess || hipMemset(e->fw.att, 0, nw) != hipSuccess) {
+    if (e->fw_cur.alloc(nw, false) != hipSuccess || e->fw_snd.alloc(nw, false) != hipSuccess ||
+        e->fw_att.alloc(nw, false) != hipSuccess || hipMemset(e->fw_cur, 0xFF, nw * 4) != hipSuccess ||
+        hipMemset(e->fw_snd, 0xFF, nw * 4) != hipSuccess || hipMemset(e->fw_att, 0, nw) != hipSuccess) {
       e->err = "hipMalloc of the FLOOD walks failed";
       return bail(GOSSIP_ENOMEM);
     }
+    e->fw.cur = e->fw_cur;
+    e->fw.snd = e->fw_snd;
+    e->fw.att = e->fw_att;
   }
-  auto alloc_raw = [&](void** p, size_t bytes) {
-    if (hipMalloc(p, bytes) != hipSuccess) {
-      e->err = "hipMalloc of " + std::to_string(bytes) + " bytes failed";
-      return false;
-    }
-    return hipMemset(*p, 0, bytes) == hipSuccess;
-  };
   if (e->aex) {  // sharded ANTIENTROPY
-    const size_t vb = std::max<size_t>((size_t)e->Nl * e->R * 4, 4);
+    const size_t vn = std::max<size_t>((size_t)e->Nl * e->R, 1);
     const size_t gw = (size_t)G * e->Nl / 64;  // bitmap words of all shards
     e->aex_rw = (e->R + 2 + 1) / 2 * 2;        // request item {p, n, row[K]}, padded to 8 B
     e->aex_pw = (e->R + 1) / 2 * 2;            // response item row[K], padded to 8 B
-    e->aex_req_cap = std::max<uint64_t>(e->nown * e->k, 1);
+    const uint64_t req_cap = std::max<uint64_t>(e->nown * e->k, 1);  // every own request
     const size_t tab = aex_block_table_words(e->nown, G);
-    if (!alloc_raw((void**)&e->V, vb) || !alloc_raw((void**)&e->Vn, vb) || !alloc_raw((void**)&e->target, 256) ||
-        !alloc_raw((void**)&e->aex_img, gw * 16) || !alloc_raw((void**)&e->aex_cnt, (G + 1) * 8) ||
-        !alloc_raw((void**)&e->aex_bcnt, tab * 4) || !alloc_raw((void**)&e->aex_boff, tab * 8) ||
-        !alloc_raw((void**)&e->aex_req, e->aex_req_cap * e->aex_rw * 4) ||
-        !alloc_raw((void**)&e->aex_loc, e->aex_req_cap * 8) ||
-        !alloc_raw((void**)&e->aex_resp_in, e->aex_req_cap * e->aex_pw * 4) || !alloc_raw((void**)&e->aex_tmp, 256) ||
-        !alloc_raw((void**)&e->aex_dirty, std::max<size_t>((e->Nl + 63) / 64, 1) * 8) ||
-        !alloc_raw((void**)&e->aex_verdict, std::max<uint64_t>(e->nown, 1)))
+    if (!alloc(e->V, vn) || !alloc(e->Vn, vn) || !alloc(e->target, 64) || !alloc(e->aex_img, gw * 2) ||
+        !alloc(e->aex_cnt, G + 1) || !alloc(e->aex_bcnt, tab) || !alloc(e->aex_boff, tab) ||
+        !alloc(e->aex_req, req_cap * e->aex_rw) || !alloc(e->aex_loc, req_cap * 2) ||
+        !alloc(e->aex_resp_in, req_cap * e->aex_pw) || !alloc(e->aex_tmp, 64) ||
+        !alloc(e->aex_dirty, std::max<size_t>((e->Nl + 63) / 64, 1)) ||
+        !alloc(e->aex_verdict, std::max<uint64_t>(e->nown, 1)))
       return bail(GOSSIP_ENOMEM);
-    if (hipHostMalloc((void**)&e->aex_cnt_h, (G + 1) * 8) != hipSuccess) return bail(GOSSIP_ENOMEM);
+    if (e->aex_cnt_h.alloc(G + 1) != hipSuccess) return bail(GOSSIP_ENOMEM);
     if (launch_aex_fill_alive(make_aex_args(e), nullptr) != hipSuccess) return bail(GOSSIP_EHIP);
   } else if (e->mode == GOSSIP_MODE_ANTIENTROPY) {
-    const size_t vb = (size_t)e->N * e->R * 4;
+    const size_t vn = (size_t)e->N * e->R;
     const size_t nw = ((size_t)e->N + 63) / 64;
-    if (!alloc_raw((void**)&e->V, vb) || !alloc_raw((void**)&e->Vn, vb) || !alloc_raw((void**)&e->target, 256) ||
-        !alloc_raw((void**)&e->alive, nw * 16) || !alloc_raw((void**)&e->alive_n, nw * 16))
+    if (!alloc(e->V, vn) || !alloc(e->Vn, vn) || !alloc(e->target, 64) || !alloc(e->alive, nw * 2) ||
+        !alloc(e->alive_n, nw * 2))
       return bail(GOSSIP_ENOMEM);
     if (launch_ae_fill_alive(e->alive, e->N, nullptr) != hipSuccess) return bail(GOSSIP_EHIP);
     e->ae_bg = ae_bin_geom(e->N, e->k);
     e->ae_bin = !(cfg->flags & GOSSIP_FLAG_AE_DIRECT_SCAN) && e->k <= 16 && ae_bin_fits(e->ae_bg);  // else the direct scan
     e->ae_dg = ae_dense_geom(e->N, e->k);
     e->ae_dbin = ae_dense_fits(e->ae_dg, e->N, e->k, e->R);  // else pull + atomicMax push + stats
-    if (e->ae_dbin && !alloc_raw((void**)&e->ae_dboff, (size_t)e->ae_dg.nreg * (e->ae_dg.nt + 1) * 2))
-      return bail(GOSSIP_ENOMEM);
+    if (e->ae_dbin && !alloc(e->ae_dboff, (size_t)e->ae_dg.nreg * (e->ae_dg.nt + 1))) return bail(GOSSIP_ENOMEM);
     if (e->ae_bin || e->ae_dbin) {
       const size_t recs = (size_t)e->ae_bg.nreg * ((size_t)e->k << e->ae_bg.rs);
-      if (!alloc_raw((void**)&e->ae_brec, recs * 4) ||
-          (e->ae_bin && !alloc_raw((void**)&e->ae_boff, (size_t)e->ae_bg.nreg * (e->ae_bg.nt + 1) * 2)))
+      if (!alloc(e->ae_brec, recs) || (e->ae_bin && !alloc(e->ae_boff, (size_t)e->ae_bg.nreg * (e->ae_bg.nt + 1))))
         return bail(GOSSIP_ENOMEM);
     }
     e->ae_aux = e->partial_d + part_len(e);
-    e->ae_aux_alias = true;
-    if (!alloc_raw((void**)&e->ae_claim, (size_t)e->N * 4) ||
-        !alloc_raw(&e->ae_pmask, (size_t)e->N * e->k * std::max<uint32_t>(1, ae_lanes(e->R) / 8)))
+    if (!alloc(e->ae_claim, e->N) ||
+        !alloc(e->ae_pmask, (size_t)e->N * e->k * std::max<uint32_t>(1, ae_lanes(e->R) / 8)))
       return bail(GOSSIP_ENOMEM);
     if (ae_alloc_lists(e, 0) != GOSSIP_OK) return bail(GOSSIP_ENOMEM);
   } else if (e->mode == GOSSIP_MODE_FLOOD) {
-    if (!alloc(&e->S, shard) || !alloc(&e->Snext, shard) || !alloc(&e->Sprev, shard) || !alloc(&e->skip, shard) ||
-        !alloc(&e->imgF, image))
-      return bail(GOSSIP_ENOMEM);
-  } else if (!alloc(&e->img[0], image) || !alloc(&e->img[1], image)) {
+    for (auto& b : e->flood_st)
+      if (!alloc(b, shard / 8)) return bail(GOSSIP_ENOMEM);
+    if (!alloc(e->imgF, image / 8)) return bail(GOSSIP_ENOMEM);
+    e->S = e->flood_st[0];
+    e->Snext = e->flood_st[1];
+    e->Sprev = e->flood_st[2];
+    e->skip = e->flood_st[3];
+  } else if (!alloc(e->img[0], image / 8) || !alloc(e->img[1], image / 8)) {
     return bail(GOSSIP_ENOMEM);
   }
   bind_slices(e);
@@ -1721,7 +1638,7 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
     // its runs of 16 records gain less than the big emit costs), profiles/r04_s
     e->bg = make_bin_geom(e->N, e->k, (e->N + kTileD - 1) / kTileD > kBigFromTiles);
     const size_t bytes = bin_bytes(e->bg);
-    if (hipMalloc(&e->bin_mem, bytes) != hipSuccess) {
+    if (e->bin_mem.alloc(bytes, false) != hipSuccess) {
       e->err = "hipMalloc of " + std::to_string(bytes) + " bytes (bins) failed";
       return bail(GOSSIP_ENOMEM);
     }
@@ -1738,13 +1655,13 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
     e->binned = true;
     if (!(cfg->flags & GOSSIP_FLAG_DENSE)) {
       const size_t fbytes = frontier_bytes(e->N);
-      if (!alloc_raw(&e->fr_mem, fbytes)) return bail(GOSSIP_ENOMEM);
+      if (!alloc(e->fr_mem, fbytes)) return bail(GOSSIP_ENOMEM);
       frontier_carve(e->N, e->fr_mem, &e->fb);
       e->bb.nzb = e->fb.nzb;
       e->bb.fullb = e->fb.fullb;
       e->frontier = true;
     }
-    if (hipHostMalloc((void**)&e->ring_h, kRing * (part_len(e) + 1) * 8, hipHostMallocMapped) != hipSuccess ||
+    if (e->ring_h.alloc(kRing * (part_len(e) + 1), hipHostMallocMapped) != hipSuccess ||
         hipHostGetDevicePointer((void**)&e->ring_d, e->ring_h, 0) != hipSuccess) {
       e->err = "round ring allocation failed";
       return bail(GOSSIP_ENOMEM);
@@ -1754,25 +1671,24 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
   if (G > 1 && G <= 1024 && e->W == 1 && e->mode >= GOSSIP_MODE_PUSH && e->mode <= GOSSIP_MODE_PUSHPULL &&
       !(cfg->flags & (GOSSIP_FLAG_DIRECT | GOSSIP_FLAG_DENSE))) {
     e->sg = SxGeom{e->N, e->Nl, e->lo, e->nown, G, e->rank, e->k, e->R};
-    if (!alloc_raw(&e->lf_mem, frontier_bytes(e->nown)) || !alloc_raw(&e->sx_mem, sx_bytes(e->sg)))
-      return bail(GOSSIP_ENOMEM);
+    if (!alloc(e->lf_mem, frontier_bytes(e->nown)) || !alloc(e->sx_mem, sx_bytes(e->sg))) return bail(GOSSIP_ENOMEM);
     frontier_carve(e->nown, e->lf_mem, &e->lf);
     e->lf.id0 = e->lo;
     sx_carve(e->sg, e->sx_mem, &e->sb);
-    if (hipHostMalloc((void**)&e->sx_host, (G + 2) * 8, hipHostMallocDefault) != hipSuccess) {
+    if (e->sx_host.alloc(G + 2) != hipSuccess) {
       e->err = "hipHostMalloc failed";
       return bail(GOSSIP_ENOMEM);
     }
     e->sx = true;
     if (!(cfg->flags & GOSSIP_FLAG_SHARD_DIRECT) && sb_path_ok(e->N, e->k, e->nown)) {
       e->sbg = make_sb_geom(e->N, e->k, e->lo, e->nown);
-      if (!alloc_raw(&e->sb_mem, sb_bytes(e->sbg))) return bail(GOSSIP_ENOMEM);
+      if (!alloc(e->sb_mem, sb_bytes(e->sbg))) return bail(GOSSIP_ENOMEM);
       sb_carve(e->sbg, e->sb_mem, &e->sbb);
       e->sbin = true;
     }
     if (xd_path_ok(e->N, e->k, e->Nl, G)) {
       e->xg = make_xd_geom(e->N, e->k, e->Nl, e->lo, e->nown, G, e->rank);
-      if (hipHostMalloc((void**)&e->xd_cnt_h, G * 4, hipHostMallocDefault) != hipSuccess) {
+      if (e->xd_cnt_h.alloc(G) != hipSuccess) {
         e->err = "hipHostMalloc failed";
         return bail(GOSSIP_ENOMEM);
       }
@@ -1780,29 +1696,22 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
     }
     // sharded sparse rounds pay off up to a larger rare fraction than on one GPU: sparse_frac_of
   }
-  if (hipHostMalloc((void**)&e->partial_h, part_len(e) * 8 + 64, hipHostMallocDefault) != hipSuccess) {
+  if (e->partial_h.alloc(part_len(e) + 8) != hipSuccess) {
     e->err = "hipHostMalloc failed";
     return bail(GOSSIP_ENOMEM);
   }
-  if (e->ae_aux_alias) e->ae_aux_h = e->partial_h + part_len(e);
+  if (e->ae_aux) e->ae_aux_h = e->partial_h + part_len(e);
   if (e->timing) {
+    bool ok = true;
     for (auto& p : e->ev)
-      for (auto& x : p)
-        if (hipEventCreate(&x) != hipSuccess) {
-          e->err = "hipEventCreate failed";
-          return bail(GOSSIP_EHIP);
-        }
-    for (auto& x : e->ev_pre)
-      if (hipEventCreate(&x) != hipSuccess) {
-        e->err = "hipEventCreate failed";
-        return bail(GOSSIP_EHIP);
-      }
+      for (auto& x : p) ok = ok && x.create() == hipSuccess;
+    for (auto& x : e->ev_pre) ok = ok && x.create() == hipSuccess;
     for (auto& p : e->evr)
-      for (auto& x : p)
-        if (hipEventCreate(&x) != hipSuccess) {
-          e->err = "hipEventCreate failed";
-          return bail(GOSSIP_EHIP);
-        }
+      for (auto& x : p) ok = ok && x.create() == hipSuccess;
+    if (!ok) {
+      e->err = "hipEventCreate failed";
+      return bail(GOSSIP_EHIP);
+    }
   }
   // the zeroing above ran on the null stream, which the engine's non-blocking
   // stream does not wait for: finish it before any engine work is enqueued
@@ -1821,7 +1730,6 @@ void gossip_destroy(gossip_engine_t* eng) {
   delete eng->tr;
   eng->tr = nullptr;
   (void)hipSetDevice(eng->device);
-  free_all(eng);
   delete eng;
 }
 
@@ -1944,15 +1852,10 @@ int gossip_set_topology_csr(gossip_engine_t* e, const uint32_t* row_ptr, const u
     for (uint32_t q = orow[u]; q < orow[u + 1]; ++q) icol[fill[ocol[q]]++] = (uint32_t)u;
   if (int rc = set_dev(e)) return rc;
   HIP_OK(e, hipStreamSynchronize(e->stream));
-  uint32_t** bufs[] = {&e->orow, &e->ocol, &e->irow, &e->icol};
-  for (uint32_t** b : bufs)
-    if (*b) {
-      HIP_OK(e, hipFree(*b));
-      *b = nullptr;
-    }
-  const size_t eb = std::max<size_t>(ocol.size(), 1) * 4, rb = (n + 1) * 4;
-  if (hipMalloc((void**)&e->orow, rb) != hipSuccess || hipMalloc((void**)&e->ocol, eb) != hipSuccess ||
-      hipMalloc((void**)&e->irow, rb) != hipSuccess || hipMalloc((void**)&e->icol, eb) != hipSuccess)
+  for (DevBuf<uint32_t>* b : {&e->orow, &e->ocol, &e->irow, &e->icol}) HIP_OK(e, b->reset());
+  const size_t en = std::max<size_t>(ocol.size(), 1), rb = (n + 1) * 4;
+  if (e->orow.alloc(n + 1, false) != hipSuccess || e->ocol.alloc(en, false) != hipSuccess ||
+      e->irow.alloc(n + 1, false) != hipSuccess || e->icol.alloc(en, false) != hipSuccess)
     return e->fail(GOSSIP_ENOMEM, "topology allocation failed");
   HIP_OK(e, hipMemcpy(e->orow, orow.data(), rb, hipMemcpyHostToDevice));
   HIP_OK(e, hipMemcpy(e->irow, irow.data(), rb, hipMemcpyHostToDevice));
@@ -2115,7 +2018,7 @@ namespace {
 // pub_d: [0, G) per-rank counts, [G] one count, [G + 2, G + 2 + part_len) partials.
 int pub_alloc(gossip_engine* e) {
   if (e->pub_d) return GOSSIP_OK;
-  HIP_OK(e, hipMalloc((void**)&e->pub_d, (e->G + 2 + part_len(e)) * 8));
+  HIP_OK(e, e->pub_d.alloc(e->G + 2 + part_len(e), false));
   return GOSSIP_OK;
 }
 uint64_t* pub_counts(gossip_engine* e) { return e->pub_d; }
@@ -2211,14 +2114,9 @@ int sx_check(gossip_engine* e, bool planned) {
   return set_dev(e);
 }
 
-int grow(gossip_engine* e, SxItem** buf, uint64_t* cap, uint64_t items) {
-  if (items <= *cap && *buf) return GOSSIP_OK;
-  const uint64_t want = std::max<uint64_t>(items + items / 4, 1024);
-  if (*buf) HIP_OK(e, hipFree(*buf));
-  *buf = nullptr;
-  *cap = 0;
-  HIP_OK(e, hipMalloc((void**)buf, want * sizeof(SxItem)));
-  *cap = want;
+// room for `items` in a receive buffer: a quarter more than asked, 1024 at least
+int grow(gossip_engine* e, DevBuf<SxItem>& buf, uint64_t items) {
+  HIP_OK(e, buf.reserve(items, std::max<uint64_t>(items + items / 4, 1024) - items));
   return GOSSIP_OK;
 }
 
@@ -2340,7 +2238,7 @@ int gossip_sparse_rare_recv(gossip_engine_t* e, uint64_t stride, void** recv) {
   if (!recv) return GOSSIP_EINVAL;
   if (int rc = sx_check(e, true)) return rc;
   if (stride > e->Nl) return e->fail(GOSSIP_EINVAL, "rare list stride %llu > nodes per shard", (unsigned long long)stride);
-  if (int rc = grow(e, &e->rare_recv, &e->rare_recv_cap, stride * e->G)) return rc;
+  if (int rc = grow(e, e->rare_recv, stride * e->G)) return rc;
   e->sx_stride = stride;
   *recv = e->rare_recv;
   return GOSSIP_OK;
@@ -2373,7 +2271,7 @@ int gossip_sparse_scan(gossip_engine_t* e, const uint64_t* counts, void** send, 
   // (the copy below lands in cb's pinned buffer after the copy that read it: same stream)
   HIP_OK(e, hipMemcpyAsync(e->sx_host, e->sb.msg_cnt, (e->G + 1) * 4, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(e, hipStreamSynchronize(e->stream));
-  const uint32_t* c = (const uint32_t*)e->sx_host;
+  const uint32_t* c = (const uint32_t*)e->sx_host.get();
   for (uint32_t q = 0; q < e->G; ++q) send_counts[q] = c[q];
   *send = e->sb.msg_out;
   return GOSSIP_OK;
@@ -2396,14 +2294,14 @@ int gossip_sparse_scan_dev(gossip_engine_t* e, const uint64_t* counts, void** se
 int gossip_sparse_msg_recv(gossip_engine_t* e, uint64_t items, void** recv) {
   if (!recv) return GOSSIP_EINVAL;
   if (int rc = sx_check(e, true)) return rc;
-  if (int rc = grow(e, &e->msg_recv, &e->msg_recv_cap, items)) return rc;
+  if (int rc = grow(e, e->msg_recv, items)) return rc;
   *recv = e->msg_recv;
   return GOSSIP_OK;
 }
 
 namespace {
 int sparse_commit_enqueue(gossip_engine* e, uint64_t items) {
-  if (items > e->msg_recv_cap) return e->fail(GOSSIP_EINVAL, "more messages than the receive buffer holds");
+  if (items > e->msg_recv.count()) return e->fail(GOSSIP_EINVAL, "more messages than the receive buffer holds");
   if (int rc = timer_begin(e, 1)) return rc;
   HIP_OK(e, sx_apply(e->lf, e->msg_recv, items, e->sx_alld, e->stream));
   HIP_OK(e, launch_frontier_commit(e->lf, e->S, e->nown, e->partial_d, e->R, e->sx_alld ? kSparseAllD : kSparseFlags,
@@ -2453,7 +2351,7 @@ int gossip_cc_send(gossip_engine_t* e, void** bits, uint64_t* bits_bytes, void**
     if (int rc = place_sb(e)) return rc;
   const uint64_t nwl = (e->Nl + 63) / 64, slot = cc_slot_words(e->Nl);
   if (!e->cc_bits) {
-    HIP_OK(e, hipMalloc((void**)&e->cc_bits, (size_t)e->G * slot * 8));
+    HIP_OK(e, e->cc_bits.alloc((size_t)e->G * slot, false));
     HIP_OK(e, hipMemsetAsync(e->cc_bits, 0, (size_t)e->G * slot * 8, e->stream));
   }
   if (int rc = sx_prepare(e)) return rc;  // exact occupancy bitmaps of S_t
@@ -2480,14 +2378,9 @@ int gossip_cc_recv(gossip_engine_t* e, uint64_t stride, void** bits_image, void*
   if (!e->cc_bits) return e->fail(GOSSIP_ESTATE, "gossip_cc_send first");
   if (stride > e->Nl) return e->fail(GOSSIP_EINVAL, "stride %llu > nodes per shard", (unsigned long long)stride);
   const uint64_t want = std::max<uint64_t>(stride * e->G, 1);
-  if (want > e->cc_vals_cap) {
+  if (want > e->cc_vals.count()) {
     HIP_OK(e, hipStreamSynchronize(e->stream));
-    if (e->cc_vals) HIP_OK(e, hipFree(e->cc_vals));
-    e->cc_vals = nullptr;
-    e->cc_vals_cap = 0;
-    const uint64_t cap = want + want / 4;
-    HIP_OK(e, hipMalloc((void**)&e->cc_vals, cap * 8));
-    e->cc_vals_cap = cap;
+    HIP_OK(e, e->cc_vals.reserve(want, want / 4));
   }
   e->cc_stride = stride;
   *bits_image = e->cc_bits;
@@ -2525,9 +2418,9 @@ int gossip_xd_classes(gossip_engine_t* e, void** send, void** image, uint64_t* b
   if (!e->xd_filt) return GOSSIP_OK;  // no filter this round: nothing to gather
   const uint64_t nwl = (e->Nl + 63) / 64;
   if (!e->xd_cls) {
-    HIP_OK(e, hipMalloc((void**)&e->xd_cls, (size_t)e->G * 2 * nwl * 8));
+    HIP_OK(e, e->xd_cls.alloc((size_t)e->G * 2 * nwl, false));
     HIP_OK(e, hipMemsetAsync(e->xd_cls, 0, (size_t)e->G * 2 * nwl * 8, e->stream));
-    HIP_OK(e, hipMalloc((void**)&e->xd_keep, e->nown + 1));
+    HIP_OK(e, e->xd_keep.alloc(e->nown + 1, false));
   }
   if (int rc = sx_prepare(e)) return rc;  // exact occupancy bitmaps of S_t
   uint64_t* own = e->xd_cls + (size_t)e->rank * 2 * nwl;
@@ -2549,10 +2442,8 @@ int xd_requests_enqueue(gossip_engine* e) {
   const XdFilter xf{e->xd_cls, (uint32_t)((e->Nl + 63) / 64), e->xd_cls_ok ? e->xd_filt : 0u, e->xd_keep};
   if (!e->xd_smem) {
     const size_t bytes = xd_send_bytes(e->xg);
-    if (hipMalloc(&e->xd_smem, bytes) != hipSuccess) {
-      e->xd_smem = nullptr;
+    if (e->xd_smem.alloc(bytes, false) != hipSuccess)
       return e->fail(GOSSIP_ENOMEM, "hipMalloc of %zu bytes (exchange send buffers) failed", bytes);
-    }
     xd_carve_send(e->xg, e->xd_smem, &e->xb);
   }
   HIP_OK(e, hipMemsetAsync(e->partial_d, 0, part_len(e) * 8, e->stream));
@@ -2594,15 +2485,12 @@ int gossip_xd_request_recv(gossip_engine_t* e, uint64_t items, void** ids, void*
   if (items >= (1ull << 31)) return e->fail(GOSSIP_EINVAL, "%llu items exceed one exchange round", (unsigned long long)items);
   if (!e->xd_rmem || items > e->xd_rcap) {
     HIP_OK(e, hipStreamSynchronize(e->stream));
-    if (e->xd_rmem) HIP_OK(e, hipFree(e->xd_rmem));
-    e->xd_rmem = nullptr;
     e->xd_rcap = 0;
+    HIP_OK(e, e->xd_rmem.reset());
     const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(items + items / 4, kXdBinRegion), (1ull << 31) - 1);
     const size_t bytes = xd_recv_bytes(e->xg, want);
-    if (hipMalloc(&e->xd_rmem, bytes) != hipSuccess) {
-      e->xd_rmem = nullptr;
+    if (e->xd_rmem.alloc(bytes, false) != hipSuccess)
       return e->fail(GOSSIP_ENOMEM, "hipMalloc of %zu bytes (exchange receive buffers) failed", bytes);
-    }
     xd_carve_recv(e->xg, want, e->xd_rmem, &e->xb);
     e->xd_rcap = want;
   }
@@ -2735,17 +2623,11 @@ int gossip_ae_requests(gossip_engine_t* e, void** send, uint64_t* send_counts) {
 int gossip_ae_request_recv(gossip_engine_t* e, uint64_t items, void** recv) {
   if (!recv) return GOSSIP_EINVAL;
   if (int rc = aex_check(e)) return rc;
-  if (items > e->aex_in_cap || !e->aex_in) {  // grow both the inbox and the replies to it
+  if (items * e->aex_rw > e->aex_in.count() || !e->aex_in) {  // grow both the inbox and the replies to it
     const uint64_t want = std::max<uint64_t>(items + items / 4, 1024);
-    for (uint32_t** b : {&e->aex_in, &e->aex_resp_out})
-      if (*b) {
-        HIP_OK(e, hipFree(*b));
-        *b = nullptr;
-      }
-    e->aex_in_cap = 0;
-    HIP_OK(e, hipMalloc((void**)&e->aex_in, want * e->aex_rw * 4));
-    HIP_OK(e, hipMalloc((void**)&e->aex_resp_out, want * e->aex_pw * 4));
-    e->aex_in_cap = want;
+    for (DevBuf<uint32_t>* b : {&e->aex_in, &e->aex_resp_out}) HIP_OK(e, b->reset());  // (both go before either comes back)
+    HIP_OK(e, e->aex_in.alloc(want * e->aex_rw, false));
+    HIP_OK(e, e->aex_resp_out.alloc(want * e->aex_pw, false));
   }
   e->aex_nin = items;
   // few items (each raises at most one own row): mark the raised rows so the next round seeds
@@ -2985,15 +2867,13 @@ uint32_t gossip_peer(uint64_t seed, uint64_t n_nodes, uint32_t node, uint32_t ro
 int gossip_philox_device(gossip_engine_t* e, const uint32_t* ctr4, const uint32_t* key2, uint32_t* out4, uint32_t n) {
   if (!e || !ctr4 || !key2 || !out4) return GOSSIP_EINVAL;
   if (int rc = set_dev(e)) return rc;
-  uint32_t *dc = nullptr, *dout = nullptr;
-  HIP_OK(e, hipMalloc((void**)&dc, (size_t)n * 16 + 16));
-  HIP_OK(e, hipMalloc((void**)&dout, (size_t)n * 16 + 16));
+  DevBuf<uint32_t> dc, dout;
+  HIP_OK(e, dc.alloc((size_t)n * 4 + 4, false));
+  HIP_OK(e, dout.alloc((size_t)n * 4 + 4, false));
   HIP_OK(e, hipMemcpy(dc, ctr4, (size_t)n * 16, hipMemcpyHostToDevice));
   HIP_OK(e, launch_philox(dc, key2[0], key2[1], dout, n, e->stream));
   HIP_OK(e, hipStreamSynchronize(e->stream));
   HIP_OK(e, hipMemcpy(out4, dout, (size_t)n * 16, hipMemcpyDeviceToHost));
-  HIP_OK(e, hipFree(dc));
-  HIP_OK(e, hipFree(dout));
   return GOSSIP_OK;
 }
 
@@ -3144,8 +3024,8 @@ bool engine_rccl_dev(const gossip_engine_t* e) { return e->rccl_dev; }
 int engine_wall_begin(gossip_engine_t* e) {
   if (!e->timing) return GOSSIP_OK;
   if (!e->wall_ev[0]) {
-    HIP_OK(e, hipEventCreate(&e->wall_ev[0]));
-    HIP_OK(e, hipEventCreate(&e->wall_ev[1]));
+    HIP_OK(e, e->wall_ev[0].create());
+    HIP_OK(e, e->wall_ev[1].create());
   }
   HIP_OK(e, hipEventRecord(e->wall_ev[0], e->stream));
   return GOSSIP_OK;

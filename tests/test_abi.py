@@ -56,6 +56,19 @@ def test_library_reads_no_environment():
         assert "getenv" not in src, name
 
 
+def test_engine_memory_is_owned():
+    """Device memory, pinned memory and events of the engine live in the owners of csrc/devmem.h
+    (freed by their destructors): engine.hip frees nothing by hand and allocates through them, so
+    a new buffer is a new member and cannot be forgotten in a hand-kept list."""
+    csrc = os.path.join(ROOT, "gossip-protocol_amd", "csrc")
+    engine = open(os.path.join(csrc, "engine.hip")).read()
+    for word in ("hipFree(", "hipHostFree(", "hipEventDestroy(", "free_all", "hipMalloc(", "hipHostMalloc("):
+        assert word not in engine, word
+    devmem = open(os.path.join(csrc, "devmem.h")).read()
+    for word in ("hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree(", "hipEventCreate(", "hipEventDestroy("):
+        assert word in devmem, word
+
+
 def test_struct_layout():
     assert C.sizeof(_abi.Config) == 64
     assert C.sizeof(_abi.RoundStats) == 40
