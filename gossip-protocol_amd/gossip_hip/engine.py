@@ -125,7 +125,8 @@ class AbiEngine:
         return getattr(self._lib, self._p + name)
 
     def supports(self, name: str) -> bool:
-        """Whether the bound library exports gossip_<name> (the CPU oracle has no sparse sharded rounds)."""
+        """Whether the bound library exports <prefix><name> (the CPU oracle has every sharded round, but not
+        the device-value calls *_dev)."""
         return hasattr(self._lib, self._p + name)
 
     def _check(self, rc: int):
@@ -260,7 +261,11 @@ class AbiEngine:
 
     # -- sparse sharded rounds (include/gossip.h; gossip_hip.sharded drives them) --
     def sharded_plan(self, total=None) -> int:
-        """-1: needs global totals (local_totals + all-reduce), 0: dense round, 1: sparse round."""
+        """The coming round's kind, or what the engine needs first: -2 ANTIENTROPY's global max vector
+        (ae_local_target, all-reduce MAX, ae_set_target), -1 the global totals (local_totals, all-reduce
+        SUM, then passed as total); 0 dense, 1 sparse, 2 ANTIENTROPY, 3 exchange dense, 4 class-coded dense,
+        5 / 6 / 7 replicated dense after the state all-gather / with no collective / after the class-coded
+        all-gather.  gossip_hip.sharded names them."""
         kind = C.c_int32()
         t = None if total is None else np.ascontiguousarray(total, dtype=np.uint64)
         self._check(self._fn("sharded_plan")(self._h, None if t is None else t.ctypes.data_as(_abi.U64P),

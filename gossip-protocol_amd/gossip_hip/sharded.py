@@ -34,6 +34,10 @@ without a GPU):
 
 The engine decides the kind from the global totals it was last given, so every
 rank takes the same branch.
+
+Each kind is written once, over the local engines L and a comm, in the shape of the library's
+own driver (csrc/multi.hip, struct Driver): sharded_round runs it on the one engine of a rank
+with the torch.distributed comm, lockstep_round on all G engines of one process with the copy comm.
 """
 from __future__ import annotations
 
@@ -43,7 +47,12 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-ITEM_WORDS = 2  # sparse exchange items are {uint64 node, uint64 value}
+# plan kinds (gossip_sharded_plan).  Below zero the engine needs something before it can plan:
+NEED_TARGET, NEED_TOTALS = -2, -1  # ANTIENTROPY's global max vector; the global totals
+# ... from zero on, the coming round: dense, sparse, ANTIENTROPY, exchange dense, class-coded dense, and
+# replicated dense after the state all-gather / with no collective / after the class-coded all-gather
+DENSE, SPARSE, ANTIENTROPY, EXCHANGE, CLASSCODED, REP_GATHER, REP, REP_CLASSCODED = range(8)
+KIND_LETTERS = "DSAXCRrQ"  # one letter per kind, in that order
 
 
 class _DevPtr:
@@ -72,26 +81,52 @@ def _device_collectives(group) -> bool:
     return dist.get_backend(group) == "nccl"
 
 
+def _calls(L, stem: str, *args, each=None) -> list:
+    """One engine call on every local engine; each: one further argument per engine."""
+    return [getattr(e, stem)(*args, *(() if each is None else (each[i],))) for i, e in enumerate(L)]
+
+
+def _width(item_bytes: int) -> int:
+    """Items travel as int64s where they are whole ones, else as int32s (the exchange round's ids)."""
+    return 4 if item_bytes % 8 else 8
+
+
+# A comm has the collectives of a round on engine memory, given one pointer (and for an
+# all-to-all one list of item counts per rank) per local engine:
+#   all_gather(recv, send, nbytes), all_gather_async(...) -> work, wait(work),
+#   all_to_all(recv, send, recv_counts, send_counts, item_bytes), max(vectors),
+# and the exchanges of what an engine call hands out as values, named by the call's stem:
+#   gather_counts(L, stem)         -> (the call's other results per engine, the count of every rank)
+#   exchange_counts(L, stem, ...)  -> (the other results, counts sent per rank, counts received)
+#   sum(L, stem, ...)              -> the sum of every rank's partials
+# Whether those values pass through the host or stay on the device (engine.<stem>_dev) is the
+# comm's business.  world: ranks; link: the bytes a rank put on its links this round; direct:
+# collectives on the device, ordered on torch's current stream.
+
 class _Comm:
-    """The collectives a round needs, on engine memory: in place over RCCL for
+    """torch.distributed among ranks of one engine each (L = [engine]): in place over RCCL for
     device engines, staged through host tensors over gloo."""
 
     def __init__(self, engine, group, direct: bool | None = None):
         self.group = group
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        # bytes this rank put on its links this round (the model of gossip_round_wall): an
-        # all-gather sends the slice to world - 1 ranks, an all-to-all what goes to other ranks,
-        # a ring all-reduce 2 (world - 1) / world of the vector
+        self.world = dist.get_world_size(group)
+        self.rank = dist.get_rank(group)
+        # the model of gossip_round_wall: an all-gather sends the slice to world - 1 ranks, an
+        # all-to-all what goes to other ranks, a ring all-reduce 2 (world - 1) / world of the vector
         self.link = 0
         self.on_device = engine.on_device
-        self.direct = engine.on_device and self.world > 1 and _device_collectives(group)
+        self.direct = engine.on_device and _device_collectives(group)
         if direct is not None:  # tests: the collectives on engine memory as RCCL would run them
-            self.direct = direct and self.world > 1
+            self.direct = direct
+        # counts and partials as device values (RCCL on device engines with the ABI v9 calls)
+        self.dev = self.direct and engine.on_device and engine.supports("round_compute_dev")
 
     def _sync(self):
         if self.on_device:
             torch.cuda.synchronize()
+
+    def _t(self, ptr: int, nbytes: int, width: int = 8) -> torch.Tensor:
+        return _as_tensor(ptr, nbytes, self.on_device, width=width)
 
     def _lb_gather(self, send: torch.Tensor):
         self.link += send.numel() * send.element_size() * (self.world - 1)
@@ -103,7 +138,8 @@ class _Comm:
     def _lb_reduce(self, t: torch.Tensor):
         self.link += 2 * (self.world - 1) * t.numel() * t.element_size() // max(self.world, 1)
 
-    def all_gather(self, recv: torch.Tensor, send: torch.Tensor):
+    def all_gather(self, recv, send, nbytes: int):
+        recv, send = self._t(recv[0], nbytes * self.world), self._t(send[0], nbytes)
         self._lb_gather(send)
         if self.direct:
             dist.all_gather_into_tensor(recv, send, group=self.group)
@@ -113,16 +149,26 @@ class _Comm:
         recv.copy_(host)
         self._sync()
 
-    def all_gather_async(self, recv: torch.Tensor, send: torch.Tensor):
+    def all_gather_async(self, recv, send, nbytes: int):
         """Device collectives: returns the pending work (the caller's stream waits on wait());
         staged collectives complete before returning None."""
         if self.direct:
+            recv, send = self._t(recv[0], nbytes * self.world), self._t(send[0], nbytes)
             self._lb_gather(send)
             return dist.all_gather_into_tensor(recv, send, group=self.group, async_op=True)
-        self.all_gather(recv, send)
+        self.all_gather(recv, send, nbytes)
         return None
 
-    def all_to_all(self, recv: torch.Tensor, send: torch.Tensor, recv_splits, send_splits):
+    def wait(self, work):
+        if work is not None:
+            work.wait()
+
+    def all_to_all(self, recv, send, recv_counts, send_counts, item_bytes: int):
+        width = _width(item_bytes)
+        recv_splits = [c * item_bytes // width for c in recv_counts[0]]
+        send_splits = [c * item_bytes // width for c in send_counts[0]]
+        recv = self._t(recv[0], sum(recv_splits) * width, width)
+        send = self._t(send[0], sum(send_splits) * width, width)
         self._lb_a2a(send, send_splits)
         if self.direct:
             dist.all_to_all_single(recv, send, output_split_sizes=recv_splits, input_split_sizes=send_splits,
@@ -138,8 +184,8 @@ class _Comm:
         t = torch.as_tensor(np.asarray(values, dtype=np.int64).copy())
         return t.cuda() if self.direct and self.on_device else t
 
-    def all_reduce_max(self, values: np.ndarray) -> np.ndarray:
-        t = self.small(np.asarray(values, dtype=np.int64))
+    def max(self, vectors) -> np.ndarray:
+        t = self.small(np.asarray(vectors[0], dtype=np.int64))
         self._lb_reduce(t)
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
         return t.cpu().numpy()
@@ -186,139 +232,210 @@ class _Comm:
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
         return t.cpu().numpy().view(np.uint64)
 
+    def _values(self, L, stem: str, *args, each=None):
+        """(the engine call's results, whether its last one is a device pointer): engine.<stem>_dev
+        where this comm takes device values and the call has that form."""
+        dev = self.dev and hasattr(L[0], stem + "_dev")
+        return _calls(L, stem + "_dev" if dev else stem, *args, each=each)[0], dev
 
-def _dev_values(engine, comm: "_Comm") -> bool:
-    """Device-side counts and partials (RCCL on device engines with the ABI v9 calls)."""
-    return comm.direct and engine.on_device and comm.world > 1 and engine.supports("round_compute_dev")
+    def gather_counts(self, L, stem: str):
+        (*head, count), dev = self._values(L, stem)
+        return [head], self.dev_all_gather_one(count) if dev else self.all_gather_small(count)
+
+    def exchange_counts(self, L, stem: str, *args):
+        (*head, counts), dev = self._values(L, stem, *args)
+        if dev:
+            counts, in_counts = self.dev_all_to_all_counts(counts)
+        else:
+            counts = [int(c) for c in counts]
+            in_counts = self.all_to_all_small(counts)
+        return [head], [counts], [in_counts]
+
+    def sum(self, L, stem: str, each=None) -> np.ndarray:
+        part, dev = self._values(L, stem, each=each)
+        return self.dev_all_reduce_sum(part, L[0].partial_len()) if dev else self.all_reduce_sum(part)
 
 
-def _plan(engine, comm: _Comm) -> int:
-    if not engine.supports("sharded_plan"):
-        return 0
-    kind = engine.sharded_plan()
-    if kind == -2:  # ANTIENTROPY: the global max vector after an injection (ncclMax over the shards)
-        t = engine.ae_local_target()
-        engine.ae_set_target(comm.all_reduce_max(t) if comm.world > 1 else t)
-        kind = engine.sharded_plan()
-    if kind < 0:  # no global totals yet (after reset / inject): all-reduce the shards' own
-        kind = engine.sharded_plan(comm.all_reduce_sum(engine.local_totals()) if comm.world > 1
-                                   else engine.local_totals())
-    return kind
+class _CopyComm:
+    """The engines of one process, device or host, one per rank in rank order (L = all of
+    them; also the one engine of a world of 1): slice copies in place of the collectives."""
+
+    link, direct = 0, False
+
+    def __init__(self, engines):
+        self.engines, self.world = engines, len(engines)
+
+    def _sync(self):
+        for d in {e.device for e in self.engines if e.on_device}:
+            torch.cuda.synchronize(d)
+
+    def _views(self, ptrs, nbytes, width: int = 8) -> list:
+        return [_as_tensor(p, n, e.on_device, e.device if e.on_device else None, width)
+                for e, p, n in zip(self.engines, ptrs, nbytes)]
+
+    def all_gather(self, recv, send, nbytes: int):
+        G, n = self.world, nbytes // 8
+        src = self._views(send, [nbytes] * G)
+        for r, dst in enumerate(self._views(recv, [nbytes * G] * G)):
+            for q in range(G):
+                if recv[r] + q * nbytes != send[q]:  # (else the own slot of an in-place gather)
+                    dst[q * n:(q + 1) * n].copy_(src[q])
+        self._sync()
+
+    def all_gather_async(self, recv, send, nbytes: int):
+        """The copies run at wait(): after the engines' own-slice kernels are on their streams."""
+        return lambda: self.all_gather(recv, send, nbytes)
+
+    def wait(self, work):
+        work()
+
+    def all_to_all(self, recv, send, recv_counts, send_counts, item_bytes: int):
+        width = _width(item_bytes)
+        w = item_bytes // width
+        src = self._views(send, [sum(c) * item_bytes for c in send_counts], width)
+        for r, dst in enumerate(self._views(recv, [sum(c) * item_bytes for c in recv_counts], width)):
+            at = 0  # rank r receives from q = 0 .. G - 1 in order
+            for q, cnt in enumerate(send_counts):
+                if cnt[r]:
+                    off = sum(cnt[:r])
+                    dst[at * w:(at + cnt[r]) * w].copy_(src[q][off * w:(off + cnt[r]) * w])
+                    at += cnt[r]
+        self._sync()
+
+    def max(self, vectors) -> np.ndarray:
+        return np.maximum.reduce(vectors)
+
+    def gather_counts(self, L, stem: str):
+        res = _calls(L, stem)
+        return [r[:-1] for r in res], [r[-1] for r in res]
+
+    def exchange_counts(self, L, stem: str, *args):
+        res = _calls(L, stem, *args)
+        counts = [[int(c) for c in r[-1]] for r in res]
+        return [r[:-1] for r in res], counts, [[c[r] for c in counts] for r in range(self.world)]
+
+    def sum(self, L, stem: str, each=None) -> np.ndarray:
+        parts = _calls(L, stem, each=each)
+        tot = np.zeros_like(parts[0])
+        for p in parts:
+            tot = tot + p  # uint64 wraps like the RCCL int64 sum
+        return tot
 
 
-def _dense_round(engine, comm: _Comm) -> np.ndarray:
-    send_p, recv_p, nbytes = engine.exchange_buffers()
+def _plan(L, comm) -> int:
+    if not L[0].supports("sharded_plan"):
+        return DENSE
+    ks = _calls(L, "sharded_plan")
+    if ks[0] == NEED_TARGET:  # after an injection (ncclMax over the shards)
+        _calls(L, "ae_set_target", comm.max(_calls(L, "ae_local_target")))
+        ks = _calls(L, "sharded_plan")
+    if ks[0] < 0:  # NEED_TOTALS (after reset / inject): all-reduce the shards' own
+        ks = _calls(L, "sharded_plan", comm.sum(L, "local_totals"))
+    assert len(set(ks)) == 1, "shards planned different rounds"
+    return ks[0]
+
+
+# -- the rounds: each returns the global sum of the partials ------------------------------------
+
+def _dense_round(L, comm) -> np.ndarray:
+    """DENSE, and REP_GATHER (the engine then computes every node of the image)."""
+    send, recv, nbytes = zip(*_calls(L, "exchange_buffers"))
     if comm.world > 1:
-        recv = _as_tensor(recv_p, nbytes * comm.world, engine.on_device)
-        send = _as_tensor(send_p, nbytes, engine.on_device)
-        # RCCL all-gather in place (the send slice lies inside the image), in flight
-        # while the engine runs the part of the round that reads only its own slice
-        work = comm.all_gather_async(recv, send)
-        engine.dense_prepare()
-        if work is not None:
-            work.wait()
-    if _dev_values(engine, comm):
-        return comm.dev_all_reduce_sum(engine.round_compute_dev(), engine.partial_len())
-    return engine.round_compute()
+        # in place (a device engine's send slice lies inside its image), in flight while the
+        # engine runs the part of the round that reads only its own slice
+        work = comm.all_gather_async(recv, send, nbytes[0])
+        _calls(L, "dense_prepare")
+        comm.wait(work)
+    return comm.sum(L, "round_compute")
 
 
-def _sparse_round(engine, comm: _Comm) -> np.ndarray:
-    w = comm.world
-    dev = _dev_values(engine, comm)
-    if dev:
-        send_p, count_p = engine.sparse_rare_dev()
-        counts = comm.dev_all_gather_one(count_p)
-    else:
-        send_p, count = engine.sparse_rare()
-        counts = comm.all_gather_small(count)
+def _sparse_round(L, comm) -> np.ndarray:
+    rare, counts = comm.gather_counts(L, "sparse_rare")
     stride = max(counts)
-    recv_p = engine.sparse_rare_recv(stride)
+    recv = _calls(L, "sparse_rare_recv", stride)
     if stride:
-        comm.all_gather(_as_tensor(recv_p, stride * 16 * w, engine.on_device),
-                        _as_tensor(send_p, stride * 16, engine.on_device))
-    if dev:
-        out_p, counts_p = engine.sparse_scan_dev(counts)
-        out_counts, in_counts = comm.dev_all_to_all_counts(counts_p)
-    else:
-        out_p, out_counts = engine.sparse_scan(counts)
-        out_counts = [int(c) for c in out_counts]
-        in_counts = comm.all_to_all_small(out_counts)
-    n_in = sum(in_counts)
-    in_p = engine.sparse_msg_recv(n_in)
+        comm.all_gather(recv, [p for p, in rare], stride * 16)
+    out, out_counts, in_counts = comm.exchange_counts(L, "sparse_scan", counts)
+    n_in = [sum(c) for c in in_counts]
+    inbox = _calls(L, "sparse_msg_recv", each=n_in)
     # every rank joins the collective, also one with nothing to send or receive (G > 2)
-    comm.all_to_all(_as_tensor(in_p, n_in * 16, engine.on_device),
-                    _as_tensor(out_p, sum(out_counts) * 16, engine.on_device),
-                    [c * ITEM_WORDS for c in in_counts], [c * ITEM_WORDS for c in out_counts])
-    if dev:
-        return comm.dev_all_reduce_sum(engine.sparse_commit_dev(n_in), engine.partial_len())
-    return engine.sparse_commit(n_in)
+    comm.all_to_all(inbox, [p for p, in out], in_counts, out_counts, 16)  # items {uint64 node, uint64 value}
+    return comm.sum(L, "sparse_commit", each=n_in)
 
 
-def _xd_round(engine, comm: _Comm) -> np.ndarray:
-    cls_p, img_p, nb = engine.xd_classes()
-    if nb and comm.world > 1:  # every shard's class bitmaps (in place): the edge filter of this round
-        comm.all_gather(_as_tensor(img_p, nb * comm.world, engine.on_device), _as_tensor(cls_p, nb, engine.on_device))
-    dv = _dev_values(engine, comm)
-    if dv:
-        ids_p, vals_p, counts_p = engine.xd_requests_dev()
-        counts, in_counts = comm.dev_all_to_all_counts(counts_p)
-    else:
-        ids_p, vals_p, counts = engine.xd_requests()
-        in_counts = comm.all_to_all_small(counts) if comm.world > 1 else counts
-    n_in, n_out = sum(in_counts), sum(counts)
-    rid_p, rval_p = engine.xd_request_recv(n_in)
-    dev = engine.on_device
-    if comm.world > 1:
-        comm.all_to_all(_as_tensor(rid_p, n_in * 4, dev, width=4), _as_tensor(ids_p, n_out * 4, dev, width=4),
-                        in_counts, counts)
-        comm.all_to_all(_as_tensor(rval_p, n_in * 8, dev), _as_tensor(vals_p, n_out * 8, dev), in_counts, counts)
-    else:
-        _as_tensor(rid_p, n_in * 4, dev, width=4).copy_(_as_tensor(ids_p, n_out * 4, dev, width=4))
-        _as_tensor(rval_p, n_in * 8, dev).copy_(_as_tensor(vals_p, n_out * 8, dev))
-    rep_p = engine.xd_serve()  # replies in the received order
-    back_p = engine.xd_response_recv()
-    if comm.world > 1:
-        comm.all_to_all(_as_tensor(back_p, n_out * 8, dev), _as_tensor(rep_p, n_in * 8, dev), counts, in_counts)
-    else:
-        _as_tensor(back_p, n_out * 8, dev).copy_(_as_tensor(rep_p, n_in * 8, dev))
-    if dv:
-        return comm.dev_all_reduce_sum(engine.xd_finish_dev(), engine.partial_len())
-    return engine.xd_finish()
+def _xd_round(L, comm, items: list | None = None) -> np.ndarray:
+    """items gets each local shard's item counts per owner."""
+    cls, img, nb = zip(*_calls(L, "xd_classes"))
+    if nb[0] and comm.world > 1:  # every shard's class bitmaps (in place): the edge filter of this round
+        comm.all_gather(img, cls, nb[0])
+    reqs, counts, in_counts = comm.exchange_counts(L, "xd_requests")
+    if items is not None:
+        items.append([list(c) for c in counts])
+    ids, vals = zip(*reqs)
+    rid, rval = zip(*_calls(L, "xd_request_recv", each=[sum(c) for c in in_counts]))
+    comm.all_to_all(rid, ids, in_counts, counts, 4)
+    comm.all_to_all(rval, vals, in_counts, counts, 8)
+    rep = _calls(L, "xd_serve")  # replies in the received order
+    back = _calls(L, "xd_response_recv")
+    comm.all_to_all(back, rep, counts, in_counts, 8)  # what a shard received from q returns to q
+    return comm.sum(L, "xd_finish")
 
 
-def _rep_round(engine, comm: _Comm) -> np.ndarray:
-    """Kind 6: the image already holds S_t of every node (the last round was replicated)."""
-    if _dev_values(engine, comm):
-        return comm.dev_all_reduce_sum(engine.round_compute_dev(), engine.partial_len())
-    return engine.round_compute()
+def _rep_round(L, comm) -> np.ndarray:
+    """REP: the image already holds S_t of every node (the last round was replicated)."""
+    return comm.sum(L, "round_compute")
 
 
-def _cc_round(engine, comm: _Comm) -> np.ndarray:
-    bits_p, nbytes, vals_p, count = engine.cc_send()
-    w, dev = comm.world, engine.on_device
-    counts = comm.all_gather_small(count) if w > 1 else [count]
+def _cc_round(L, comm) -> np.ndarray:
+    """CLASSCODED, and REP_CLASSCODED (the engine then computes every node of the image)."""
+    sends, counts = comm.gather_counts(L, "cc_send")
+    bits, nbytes, vals = zip(*sends)
     stride = max(counts)
-    img_p, rvals_p = engine.cc_recv(stride)
-    if w > 1:
+    img, rvals = zip(*_calls(L, "cc_recv", stride))
+    if comm.world > 1:
         # the bitmaps in place (the own slot lies inside the image); the mixed words padded to
         # the stride.  Both in flight while the engine runs the own-slice part of the round.
-        works = [comm.all_gather_async(_as_tensor(img_p, nbytes * w, dev), _as_tensor(bits_p, nbytes, dev))]
+        works = [comm.all_gather_async(img, bits, nbytes[0])]
         if stride:
-            works.append(comm.all_gather_async(_as_tensor(rvals_p, stride * 8 * w, dev),
-                                               _as_tensor(vals_p, stride * 8, dev)))
-        engine.dense_prepare()
+            works.append(comm.all_gather_async(rvals, vals, stride * 8))
+        _calls(L, "dense_prepare")
         for work in works:
-            if work is not None:
-                work.wait()
-    elif count:
-        _as_tensor(rvals_p, count * 8, dev).copy_(_as_tensor(vals_p, count * 8, dev))
-    engine.cc_expand(counts)
-    if _dev_values(engine, comm):
-        return comm.dev_all_reduce_sum(engine.round_compute_dev(), engine.partial_len())
-    return engine.round_compute()
+            comm.wait(work)
+    elif stride:
+        comm.all_gather(rvals, vals, stride * 8)
+    _calls(L, "cc_expand", counts)
+    return comm.sum(L, "round_compute")
 
 
-def _bind_stream(engine, comm: _Comm) -> bool:
+def _ae_round(L, comm) -> np.ndarray:
+    rw, pw = L[0].ae_item_words(0), L[0].ae_item_words(1)  # uint32 words, even: whole int64s
+    send, recv, nbytes = zip(*_calls(L, "exchange_buffers"))  # own stale words -> every shard's image
+    if comm.world > 1:
+        comm.all_gather(recv, send, nbytes[0])
+    reqs, counts, in_counts = comm.exchange_counts(L, "ae_requests")
+    inbox = _calls(L, "ae_request_recv", each=[sum(c) for c in in_counts])
+    # (every rank joins, also one with nothing to send or receive; a shard sends itself nothing)
+    comm.all_to_all(inbox, [p for p, in reqs], in_counts, counts, rw * 4)
+    resp = _calls(L, "ae_serve")  # replies in the received order
+    back = _calls(L, "ae_response_recv")
+    comm.all_to_all(back, resp, counts, in_counts, pw * 4)
+    return comm.sum(L, "ae_finish")
+
+
+_ROUNDS = {DENSE: _dense_round, SPARSE: _sparse_round, ANTIENTROPY: _ae_round, EXCHANGE: _xd_round,
+           CLASSCODED: _cc_round, REP_GATHER: _dense_round, REP: _rep_round, REP_CLASSCODED: _cc_round}
+
+
+def _round(L, comm, kinds: list | None = None, items: list | None = None):
+    """Plan, the round of that kind, commit -> (kind, every local engine's stats)."""
+    kind = _plan(L, comm)
+    if kinds is not None:
+        kinds.append(kind)
+    total = _xd_round(L, comm, items) if kind == EXCHANGE else _ROUNDS[kind](L, comm)
+    return kind, _calls(L, "round_commit", total)
+
+
+def _bind_stream(engine, comm) -> bool:
     """Device collectives are enqueued on torch's current stream (the RCCL stream waits for
     it, and work.wait() / a synchronous collective make it wait in turn): the engine must
     launch on that same stream, or its kernels could read the image before the all-gather
@@ -328,34 +445,11 @@ def _bind_stream(engine, comm: _Comm) -> bool:
     caller clears it when the round ends (sharded_round), so the flag never outlives the round
     that bound the stream (a later host driver, staged collectives or another stream get the
     sync back)."""
-    if comm.direct and comm.on_device:
+    if comm.direct and engine.on_device:
         engine.set_stream(torch.cuda.current_stream().cuda_stream)
         engine.set_param("ordered_collectives", 1)
         return True
     return False
-
-
-def _ae_round(engine, comm: _Comm) -> np.ndarray:
-    w = comm.world
-    rw, pw = engine.ae_item_words(0), engine.ae_item_words(1)  # uint32 words, even: whole int64s
-    send_p, recv_p, nbytes = engine.exchange_buffers()  # own stale words -> every shard's image
-    if w > 1:
-        comm.all_gather(_as_tensor(recv_p, nbytes * w, engine.on_device), _as_tensor(send_p, nbytes, engine.on_device))
-    req_p, counts = engine.ae_requests()
-    in_counts = comm.all_to_all_small(counts) if w > 1 else counts
-    n_in = sum(in_counts)
-    in_p = engine.ae_request_recv(n_in)
-    if w > 1:  # (every rank joins, also one with nothing to send or receive)
-        comm.all_to_all(_as_tensor(in_p, n_in * rw * 4, engine.on_device),
-                        _as_tensor(req_p, sum(counts) * rw * 4, engine.on_device),
-                        [c * rw // 2 for c in in_counts], [c * rw // 2 for c in counts])
-    resp_p = engine.ae_serve()  # replies in the received order
-    back_p = engine.ae_response_recv()
-    if w > 1:
-        comm.all_to_all(_as_tensor(back_p, sum(counts) * pw * 4, engine.on_device),
-                        _as_tensor(resp_p, n_in * pw * 4, engine.on_device),
-                        [c * pw // 2 for c in counts], [c * pw // 2 for c in in_counts])
-    return engine.ae_finish()
 
 
 def sharded_round(engine, group=None, kinds: list | None = None, direct: bool | None = None,
@@ -365,28 +459,11 @@ def sharded_round(engine, group=None, kinds: list | None = None, direct: bool | 
     collectives that feed it.  kinds: the round's plan kind is appended to it.  direct (tests):
     force the in-place collective path that RCCL takes, also for host engines over gloo.
     trace: gets {"kind", "link_bytes"} of the round (the bytes this rank sent over its links)."""
-    comm = _Comm(engine, group, direct)
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    comm = _Comm(engine, group, direct) if world > 1 else _CopyComm([engine])
     ordered = _bind_stream(engine, comm)
     try:
-        kind = _plan(engine, comm)
-        if kinds is not None:
-            kinds.append(kind)
-        if kind == 2:
-            partial = _ae_round(engine, comm)
-        elif kind == 3:
-            partial = _xd_round(engine, comm)
-        elif kind in (4, 7):  # 7: the class-coded all-gather, then the replicated round
-            partial = _cc_round(engine, comm)
-        elif kind == 1:
-            partial = _sparse_round(engine, comm)
-        elif kind == 6:
-            partial = _rep_round(engine, comm)
-        else:  # 0, and 5 (the state all-gather, then the replicated round)
-            partial = _dense_round(engine, comm)
-        # the device-value path returns the global sum already (one all-reduce on engine memory)
-        if comm.world > 1 and not (kind != 2 and _dev_values(engine, comm)):
-            partial = comm.all_reduce_sum(partial)
-        st = engine.round_commit(partial)
+        kind, (st,) = _round([engine], comm, kinds)
         if trace is not None:
             trace.append({"kind": kind, "link_bytes": comm.link})
         return st
@@ -462,204 +539,23 @@ def sharded_run(engine, max_rounds: int, group=None, kinds: list | None = None, 
 
 # -- single-process driver ---------------------------------------------------
 
-def _sync_all(engines):
-    for d in {e.device for e in engines if e.on_device}:
-        torch.cuda.synchronize(d)
-
-
-def _lockstep_sum(parts):
-    tot = np.zeros_like(parts[0])
-    for p in parts:
-        tot = tot + p  # uint64 wraps like the RCCL int64 sum
-    return tot
-
-
-def _lockstep_dense(engines):
-    G = len(engines)
-    bufs = [e.exchange_buffers() for e in engines]
-    for e in engines:  # on the engines' streams, concurrent with the copies below (disjoint slices)
-        e.dense_prepare()
-    for e, (_, recv_p, nbytes) in zip(engines, bufs):
-        recv = _as_tensor(recv_p, nbytes * G, True, e.device)
-        for q, (send_q, _, _) in enumerate(bufs):
-            if engines[q] is not e:
-                recv[q * nbytes // 8:(q + 1) * nbytes // 8].copy_(_as_tensor(send_q, nbytes, True, engines[q].device))
-    _sync_all(engines)
-    return [e.round_compute() for e in engines]
-
-
-def _lockstep_sparse(engines):
-    G = len(engines)
-    rare = [e.sparse_rare() for e in engines]
-    counts = [c for _, c in rare]
-    stride = max(counts)
-    recvs = [e.sparse_rare_recv(stride) for e in engines]
-    if stride:
-        for e, rp in zip(engines, recvs):
-            recv = _as_tensor(rp, stride * 16 * G, True, e.device)
-            for q, (sp, _) in enumerate(rare):
-                recv[q * stride * ITEM_WORDS:(q + 1) * stride * ITEM_WORDS].copy_(
-                    _as_tensor(sp, stride * 16, True, engines[q].device))
-        _sync_all(engines)
-    scans = [e.sparse_scan(counts) for e in engines]
-    outs = [(p, [int(c) for c in cnt]) for p, cnt in scans]
-    n_in = [sum(outs[q][1][r] for q in range(G)) for r in range(G)]
-    ins = [e.sparse_msg_recv(n) for e, n in zip(engines, n_in)]
-    for r in range(G):
-        dst = _as_tensor(ins[r], n_in[r] * 16, True, engines[r].device)
-        at = 0
-        for q, (sp, cnt) in enumerate(outs):
-            off = sum(cnt[:r])
-            if cnt[r]:
-                src = _as_tensor(sp, sum(cnt) * 16, True, engines[q].device)
-                dst[at * ITEM_WORDS:(at + cnt[r]) * ITEM_WORDS].copy_(src[off * ITEM_WORDS:(off + cnt[r]) * ITEM_WORDS])
-                at += cnt[r]
-    _sync_all(engines)
-    return [e.sparse_commit(n) for e, n in zip(engines, n_in)]
-
-
-def _lockstep_ae(engines):
-    G = len(engines)
-    rw, pw = engines[0].ae_item_words(0), engines[0].ae_item_words(1)
-    bufs = [e.exchange_buffers() for e in engines]
-    for e, (_, recv_p, nbytes) in zip(engines, bufs):  # all-gather of the stale words
-        recv = _as_tensor(recv_p, nbytes * G, True, e.device)
-        for q, (send_q, _, _) in enumerate(bufs):
-            if engines[q] is not e:
-                recv[q * nbytes // 8:(q + 1) * nbytes // 8].copy_(_as_tensor(send_q, nbytes, True, engines[q].device))
-    _sync_all(engines)
-    reqs = [e.ae_requests() for e in engines]  # (ptr, counts[owner])
-    n_in = [sum(reqs[q][1][r] for q in range(G)) for r in range(G)]
-    inbox = [e.ae_request_recv(n) for e, n in zip(engines, n_in)]
-    w64 = rw // 2
-    for r in range(G):  # all-to-all: owner r receives from q = 0..G-1 in order
-        dst = _as_tensor(inbox[r], n_in[r] * rw * 4, True, engines[r].device)
-        at = 0
-        for q, (rp, cnt) in enumerate(reqs):
-            if cnt[r]:
-                src = _as_tensor(rp, sum(cnt) * rw * 4, True, engines[q].device)
-                off = sum(cnt[:r])
-                dst[at * w64:(at + cnt[r]) * w64].copy_(src[off * w64:(off + cnt[r]) * w64])
-                at += cnt[r]
-    _sync_all(engines)
-    resp = [e.ae_serve() for e in engines]
-    back = [e.ae_response_recv() for e in engines]
-    p64 = pw // 2
-    for q, (_, cnt) in enumerate(reqs):  # replies return to requester q in its request order
-        dst = _as_tensor(back[q], sum(cnt) * pw * 4, True, engines[q].device)
-        at = 0
-        for r in range(G):
-            if cnt[r]:
-                src = _as_tensor(resp[r], n_in[r] * pw * 4, True, engines[r].device)
-                start = sum(reqs[q2][1][r] for q2 in range(q))  # where q's items landed in r's inbox
-                dst[at * p64:(at + cnt[r]) * p64].copy_(src[start * p64:(start + cnt[r]) * p64])
-                at += cnt[r]
-    _sync_all(engines)
-    return [e.ae_finish() for e in engines]
-
-
-def _lockstep_xd(engines, items: list | None = None):
-    """Exchange round of G engines in one process (device or host engines: copies in place of the
-    collectives); items gets each shard's per-owner item counts."""
-    G = len(engines)
-
-    def view(e, ptr, nbytes, width=8):
-        return _as_tensor(ptr, nbytes, e.on_device, e.device if e.on_device else None, width=width)
-
-    cls = [e.xd_classes() for e in engines]
-    if cls[0][2]:  # the class bitmaps of every shard into every image (the own slot is in place)
-        nb = cls[0][2]
-        for e, (_, img_p, _) in zip(engines, cls):
-            img = view(e, img_p, nb * G)
-            for q, (send_q, _, _) in enumerate(cls):
-                if engines[q] is not e:
-                    img[q * nb // 8:(q + 1) * nb // 8].copy_(view(engines[q], send_q, nb))
-        _sync_all(engines)
-    reqs = [e.xd_requests() for e in engines]  # (ids, vals, counts[owner])
-    if items is not None:
-        items.append([list(r[2]) for r in reqs])
-    n_in = [sum(reqs[q][2][r] for q in range(G)) for r in range(G)]
-    inbox = [e.xd_request_recv(n) for e, n in zip(engines, n_in)]
-    for r in range(G):  # all-to-all: owner r receives from q = 0..G-1 in order
-        di = view(engines[r], inbox[r][0], n_in[r] * 4, width=4)
-        dv = view(engines[r], inbox[r][1], n_in[r] * 8)
-        at = 0
-        for q, (ip, vp, cnt) in enumerate(reqs):
-            if cnt[r]:
-                off, tot = sum(cnt[:r]), sum(cnt)
-                si = view(engines[q], ip, tot * 4, width=4)
-                sv = view(engines[q], vp, tot * 8)
-                di[at:at + cnt[r]].copy_(si[off:off + cnt[r]])
-                dv[at:at + cnt[r]].copy_(sv[off:off + cnt[r]])
-                at += cnt[r]
-    _sync_all(engines)
-    reps = [e.xd_serve() for e in engines]
-    back = [e.xd_response_recv() for e in engines]
-    for q, (_, _, cnt) in enumerate(reqs):  # replies return to q in its send order
-        dst = view(engines[q], back[q], sum(cnt) * 8)
-        at = 0
-        for r in range(G):
-            if cnt[r]:
-                src = view(engines[r], reps[r], n_in[r] * 8)
-                start = sum(reqs[q2][2][r] for q2 in range(q))  # where q's items landed in r's inbox
-                dst[at:at + cnt[r]].copy_(src[start:start + cnt[r]])
-                at += cnt[r]
-    _sync_all(engines)
-    return [e.xd_finish() for e in engines]
-
-
-def _lockstep_cc(engines):
-    G = len(engines)
-    sends = [e.cc_send() for e in engines]  # (bits, bits bytes, mixed words, count)
-    counts = [c for _, _, _, c in sends]
-    stride = max(counts)
-    recvs = [e.cc_recv(stride) for e in engines]
-    for e in engines:  # the own-slice part, on the engines' streams
-        e.dense_prepare()
-    for e, (img_p, vals_p) in zip(engines, recvs):
-        nb = sends[0][1]
-        img = _as_tensor(img_p, nb * G, True, e.device)
-        vals = _as_tensor(vals_p, stride * 8 * G, True, e.device)
-        for q, (bp, _, sp, _) in enumerate(sends):
-            if engines[q] is not e:
-                img[q * nb // 8:(q + 1) * nb // 8].copy_(_as_tensor(bp, nb, True, engines[q].device))
-            if stride:
-                vals[q * stride:(q + 1) * stride].copy_(_as_tensor(sp, stride * 8, True, engines[q].device))
-    _sync_all(engines)
-    for e in engines:
-        e.cc_expand(counts)
-    return [e.round_compute() for e in engines]
+def lockstep_round(engines, items: list | None = None):
+    """One round of G shard engines in one process (one per GPU, several on one, or host
+    engines), in rank order: the round of sharded_round with copies in place of the collectives.
+    Returns (kind, stats).  items (exchange rounds): gets each shard's item counts per owner."""
+    kind, st = _round(engines, _CopyComm(engines), items=items)
+    assert all(s == st[0] for s in st)
+    return kind, st[0]
 
 
 def lockstep_run(engines, max_rounds: int, items: list | None = None):
-    """One process driving G shard engines (one per GPU, or several on one) through the
-    same rounds as sharded_run, with device copies in place of the collectives.
-    Returns (per-round stats, per-round kind: 0 dense / 1 sparse / 2 ANTIENTROPY / 3 exchange dense /
-    4 class-coded dense / 5, 7, 6 replicated dense after the all-gather, after the class-coded one, or
-    without any).  items (exchange rounds; host engines too): per round, each shard's
-    item counts per owner."""
+    """lockstep_round until converged.  Returns (per-round stats, per-round kind: DENSE ..
+    REP_CLASSCODED above).  items: as for lockstep_round, one entry per exchange round."""
     stats, kinds = [], []
     for _ in range(max_rounds):
-        ks = [e.sharded_plan() for e in engines]
-        if ks[0] == -2:  # ANTIENTROPY: global max vector = elementwise max of the shards' (ncclMax)
-            t = np.maximum.reduce([e.ae_local_target() for e in engines])
-            for e in engines:
-                e.ae_set_target(t)
-            ks = [e.sharded_plan() for e in engines]
-        if ks[0] == -1:
-            tot = _lockstep_sum([e.local_totals() for e in engines])
-            ks = [e.sharded_plan(tot) for e in engines]
-        assert len(set(ks)) == 1
-        kinds.append(ks[0])
-        if ks[0] == 3:
-            parts = _lockstep_xd(engines, items)
-        else:
-            parts = {1: _lockstep_sparse, 2: _lockstep_ae, 4: _lockstep_cc, 7: _lockstep_cc,
-                     6: lambda es: [e.round_compute() for e in es]}.get(ks[0], _lockstep_dense)(engines)
-        tot = _lockstep_sum(parts)
-        st = [e.round_commit(tot) for e in engines]
-        assert all(s == st[0] for s in st)
-        stats.append(st[0])
-        if st[0]["converged"]:
+        kind, st = lockstep_round(engines, items)
+        kinds.append(kind)
+        stats.append(st)
+        if st["converged"]:
             break
     return stats, kinds

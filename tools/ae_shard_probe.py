@@ -82,23 +82,15 @@ for rep in range(2):
             lg.clear()
         for te in tes:
             te.recv = 0
-        ks = [e.sharded_plan() for e in engines]
-        if ks[0] == -2:
-            tgt = np.maximum.reduce([te.ae_local_target() for te in tes])
-            for te in tes:
-                te.ae_set_target(tgt)
-            ks = [e.sharded_plan() for e in engines]
-        assert ks[0] == 2, ks
-        parts = sh._lockstep_ae(tes)
-        tot = sh._lockstep_sum(parts)
-        st = [te.round_commit(tot) for te in tes]
+        kind, st = sh.lockstep_round(tes)
+        assert kind == sh.ANTIENTROPY, kind
         per_rank = np.mean([sum(ms for _, ms in lg) for lg in logs])
         calls = {}
         for lg in logs:
             for name, ms in lg:
                 calls[name] = calls.get(name, 0.0) + ms / len(logs)
-        rounds.append((t, per_rank, tes[0].recv, int(st[0]["alive_nodes"]), int(st[0]["full_nodes"]), calls))
-        if st[0]["converged"]:
+        rounds.append((t, per_rank, tes[0].recv, int(st["alive_nodes"]), int(st["full_nodes"]), calls))
+        if st["converged"]:
             break
     if rep == 1:
         for t, ms, rb, alive, full, calls in rounds:

@@ -20,7 +20,7 @@ if os.environ.get("GOSSIP_LIB"):  # a library variant (tools/build_variants.sh)
 G = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 LG = int(sys.argv[2]) if len(sys.argv) > 2 else 24
 CALLS = ("sparse_rare", "sparse_scan", "sparse_commit", "dense_prepare", "round_compute", "exchange_buffers",
-         "local_totals", "xd_classes", "xd_requests", "xd_request_recv", "xd_serve", "xd_response_recv", "xd_finish",
+         "xd_classes", "xd_requests", "xd_request_recv", "xd_serve", "xd_response_recv", "xd_finish",
          "cc_send", "cc_recv", "cc_expand")
 # argv[3:]: gossip_set_param knobs as name=value (e.g. xd_shards=0: dense rounds on the state all-gather)
 PARAMS = {a.split("=")[0]: float(a.split("=")[1]) for a in sys.argv[3:]}
@@ -72,28 +72,14 @@ for rep in range(2):
     for t in range(64):
         for l in logs: l.clear()
         for te in tes: te.gathered = 0
-        ks = [e.sharded_plan() for e in engines]
-        if ks[0] < 0:
-            tot = sh._lockstep_sum([e.local_totals() for e in engines]); ks = [e.sharded_plan(tot) for e in engines]
-        if ks[0] == 1:
-            parts = sh._lockstep_sparse(tes)
-        elif ks[0] == 3:
-            parts = sh._lockstep_xd(tes)
-        elif ks[0] in (4, 7):  # (7: class-coded all-gather, then the replicated round)
-            parts = sh._lockstep_cc(tes)
-        elif ks[0] == 6:  # replicated on the whole image: no exchange
-            parts = [te.round_compute() for te in tes]
-        else:
-            parts = sh._lockstep_dense(tes)
-        tot = sh._lockstep_sum(parts)
-        st = [e.round_commit(tot) for e in engines]
+        k, st = sh.lockstep_round(tes)
         per_rank = np.mean([sum(ms for _, ms in l) for l in logs])
         calls = {}
         for l in logs:
             for name, ms in l:
                 calls[name] = calls.get(name, 0.0) + ms / len(logs)
-        rounds.append((t, ks[0], per_rank, int(st[0]["full_nodes"]), calls, tes[0].gathered))
-        if st[0]["converged"]:
+        rounds.append((t, k, per_rank, int(st["full_nodes"]), calls, tes[0].gathered))
+        if st["converged"]:
             break
     if rep == 1:
         for t, k, ms, full, calls, gb in rounds:
@@ -110,4 +96,4 @@ for rep in range(2):
         print(f"G={G} plan link_gbps={PARAMS.get('link_gbps', 76.0)}: modelled per-rank wall "
               f"{sum(r[2] for r in rounds) + link_ms:.2f} ms = device {sum(r[2] for r in rounds):.2f} + "
               f"link {link_ms:.2f} (at {bw:g} GB/s per link); kinds "
-              f"{''.join('DSAXCRrQ'[r[1]] for r in rounds)}", flush=True)
+              f"{''.join(sh.KIND_LETTERS[r[1]] for r in rounds)}", flush=True)
