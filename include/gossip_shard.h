@@ -52,12 +52,16 @@ int gossip_round_commit(gossip_engine_t* eng, const uint64_t* total, gossip_roun
  *            kind 4, then gossip_round_compute runs the whole image's round on every rank;
  *   kind  6: replicated dense round with the image already whole: gossip_round_compute only;
  *   kind  1: sparse round:
- *     gossip_sparse_rare(&send, &count)        own rare nodes, 16-B items {node, value}
+ *     gossip_sparse_rare(&send, &count)        own rare nodes (nonzero ones, or not-full ones
+ *                                              when N - full < nonzero on the global totals),
+ *                                              16-B items {global node id, S_t}, in id order
  *     all-gather of count, stride = max count
  *     gossip_sparse_rare_recv(stride, &recv)   room for G * stride items; all-gather
  *                                              stride items from every rank into it
  *     gossip_sparse_scan(counts, &send, send_counts[G])  pushes for other shards,
- *                                              grouped by owner (16-B items)
+ *                                              grouped by owner, 16-B items {node at its
+ *                                              owner, bits the peer lacks (never 0)}; no order
+ *                                              inside a group; send_counts[own rank] is 0
  *     all-to-all of the counts, then of the items (owner q gets send_counts[q])
  *     gossip_sparse_msg_recv(total_in, &recv)  room for the incoming items
  *     gossip_sparse_commit(total_in, partial)  -> all-reduce(SUM) -> gossip_round_commit.
@@ -103,7 +107,12 @@ int gossip_ae_finish(gossip_engine_t* eng, uint64_t* partial);
  * sender becomes one item for p's owner: id = (p - owner * Nl) | GOSSIP_XD_NO_PUSH /
  * GOSSIP_XD_NO_PULL flags (uint32) and S_t[n] (uint64, 0 without a push), in two arrays.
  * The owner ORs the pushes into S_{t+1}[p] and answers each pull with S_t[p] (uint64, in
- * the received order); the sender's owner ORs the replies into S_{t+1}[n].
+ * the received order); the sender's owner ORs the replies into S_{t+1}[n].  Every received
+ * item has a reply slot, so the reply all-to-all swaps the request counts; the reply to an
+ * item flagged NO_PULL is 0.  Items for the own rank's nodes are items like any other: they
+ * are in send_counts[own rank] and pass through the all-to-alls (a sparse round, above, sends
+ * the own shard nothing: send_counts[own rank] is 0 there).  The order of the items inside one
+ * owner's group is not defined.
  * Per round, after gossip_sharded_plan -> kind 3:
  *   gossip_xd_classes(&send, &image, &bytes)          bytes > 0: this round drops the one-way
  *                                                      edges that move nothing (a pull-only edge
@@ -112,7 +121,12 @@ int gossip_ae_finish(gossip_engine_t* eng, uint64_t* partial);
  *                                                      bytes from every rank's send into image (the
  *                                                      own slot is send: in place).  A shard's slot,
  *                                                      nwl = ceil(Nl / 64): [nz: nwl uint64][full:
- *                                                      nwl uint64], occupancy bitmaps of S_t.
+ *                                                      nwl uint64], occupancy bitmaps of S_t; the
+ *                                                      bits past the shard's last own node are 0.
+ *                                                      bytes > 0 iff, on the global totals of S_t,
+ *                                                      more than xd_filter_frac of the nodes are
+ *                                                      empty (modes that pull) or full (modes that
+ *                                                      push), and fanout <= 8.
  *                                                      Skipping the call runs the round unfiltered
  *                                                      (same result, more items).
  *   gossip_xd_requests(&ids, &vals, send_counts[G])   items grouped by owner
@@ -159,6 +173,8 @@ int gossip_xd_finish_dev(gossip_engine_t* eng, const uint64_t** partial);
  * nodes (nonzero, not full) before each bitmap word, and the words of its mixed nodes in id
  * order; empty and full nodes are implied.  A shard's slot, nwl = ceil(Nl / 64):
  * [nz: nwl uint64][full: nwl uint64][prefix: nwl uint32, padded to 8 bytes] = bits_bytes.
+ * A shard that owns fewer than Nl nodes (the last one, or none at all) writes zeros past its
+ * last own node: bitmap bits, the prefix entries of words without an own node, the padding.
  * Per round, after gossip_sharded_plan -> kind 4:
  *   gossip_cc_send(&bits, &bits_bytes, &vals, &count)  own slot, own count mixed words
  *   all-gather of count, stride = max count
