@@ -30,6 +30,7 @@
 #include "kernels.h"
 #include "multi.h"
 #include "philox.h"
+#include "topo_peers.h"
 
 using namespace gossip;
 
@@ -96,6 +97,7 @@ struct gossip_engine {
   DevBuf<uint64_t> scratch_d;  // 8 B
   DevBuf<uint32_t> orow, ocol, irow, icol;
   bool has_topo = false;
+  bool topo_peers = false;  // GOSSIP_FLAG_TOPO_PEERS: random modes draw their peers from the rows
   // stall mode, random modes: streak per node, all N nodes on every shard
   DevBuf<uint8_t> stall_d;
   // FLOOD with faults, one shard: per out-edge pending values and first senders
@@ -299,6 +301,23 @@ int set_dev(gossip_engine* e) {
     e->ae_v_zero = false;
     HIP_OK(e, hipMemsetAsync(e->V, 0, e->N * e->R * 4, e->stream));
   }
+  return GOSSIP_OK;
+}
+
+// FLOOD and the random modes over the topology read rows that a caller must have sent
+int need_topo(gossip_engine* e) {
+  if (e->has_topo) return GOSSIP_OK;
+  if (e->mode == GOSSIP_MODE_FLOOD) return e->fail(GOSSIP_ESTATE, "FLOOD needs a topology");
+  if (e->topo_peers) return e->fail(GOSSIP_ESTATE, "GOSSIP_FLAG_TOPO_PEERS needs a topology");
+  return GOSSIP_OK;
+}
+
+// stall streaks after round t (random modes), over the peers that round drew
+int stall_after_round(gossip_engine* e, uint32_t t) {
+  if (e->topo_peers)
+    HIP_OK(e, launch_stall_update_topo(e->stall_d, e->N, e->k, t, e->key0, e->key1, e->fa, e->orow, e->ocol, e->stream));
+  else
+    HIP_OK(e, launch_stall_update(e->stall_d, e->N, e->k, t, e->key0, e->key1, e->fa, e->stream));
   return GOSSIP_OK;
 }
 
@@ -862,7 +881,7 @@ int launch_round_path(gossip_engine* e, uint32_t t, bool sparse, uint32_t maj, b
   HIP_OK(e, launch_round_snapshot(e->partial_d, rs, e->stream));
   // stall streaks after round t (gossip_round_commit does it for rounds not run from here)
   if (e->stall_d && slot >= 0)
-    HIP_OK(e, launch_stall_update(e->stall_d, e->N, e->k, t, e->key0, e->key1, e->fa, e->stream));
+    if (int rc = stall_after_round(e, t)) return rc;
   return GOSSIP_OK;
 }
 
@@ -1335,7 +1354,8 @@ int compute_round(gossip_engine* e, const uint64_t* gathered) {
     // timer 0 covers the whole S_t -> S_{t+1} transform (seed copy + round kernel)
     if ((rc = timer_begin(e, 0))) return rc;
     HIP_OK(e, hipMemcpyAsync(e->Snext, e->S, bytes, hipMemcpyDeviceToDevice, e->stream));
-    HIP_OK(e, launch_round_random(a, e->stream));
+    if (e->topo_peers) HIP_OK(e, launch_round_topo(a, e->stream));  // peers from the rows
+    else HIP_OK(e, launch_round_random(a, e->stream));
     if ((rc = timer_end(e, 0))) return rc;
   }
   if ((rc = timer_begin(e, 1))) return rc;
@@ -1483,6 +1503,11 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
     g_create_error = "fanout must be in [1, 64]";
     return GOSSIP_EINVAL;
   }
+  if ((cfg->flags & GOSSIP_FLAG_TOPO_PEERS) &&
+      (cfg->mode == GOSSIP_MODE_FLOOD || cfg->mode == GOSSIP_MODE_ANTIENTROPY)) {
+    g_create_error = "GOSSIP_FLAG_TOPO_PEERS applies to PUSH, PULL and PUSHPULL (FLOOD sends to the whole row)";
+    return GOSSIP_EINVAL;
+  }
   const uint32_t G = cfg->shard_count ? cfg->shard_count : 1;
   if (cfg->shard_rank >= G) {
     g_create_error = "shard_rank >= shard_count";
@@ -1536,6 +1561,9 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
   e->fa = Faults{cfg->edge_loss, cfg->partitions, cfg->n_nodes};
   e->timing = (cfg->flags & GOSSIP_FLAG_TIMING) != 0;
   e->flood_edges = e->mode == GOSSIP_MODE_FLOOD && faulty;
+  e->topo_peers = (cfg->flags & GOSSIP_FLAG_TOPO_PEERS) != 0;
+  // such engines run the direct kernels: never binned, no sparse-sharded or exchange state
+  const uint32_t direct_flags = GOSSIP_FLAG_DIRECT | GOSSIP_FLAG_TOPO_PEERS;
   e->fw.D = cfg->stall_rounds;
 
   auto bail = [&](int rc) {
@@ -1631,7 +1659,7 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
     return bail(GOSSIP_ENOMEM);
   }
   bind_slices(e);
-  if (e->mode != GOSSIP_MODE_FLOOD && e->mode != GOSSIP_MODE_ANTIENTROPY && !(cfg->flags & GOSSIP_FLAG_DIRECT) &&
+  if (e->mode != GOSSIP_MODE_FLOOD && e->mode != GOSSIP_MODE_ANTIENTROPY && !(cfg->flags & direct_flags) &&
       bin_path_ok(e->N, e->k, e->W, G)) {
     // past kBigFromTiles tiles the emit regions double (longer runs per tile, binned.hip V = 4, 5):
     // per dense round 2^25 nodes 1135 -> 1094 us, 2^26 2981 -> 2582 us; 2^24 slower (521 -> 583 us:
@@ -1669,7 +1697,7 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
     std::memset(e->ring_h, 0, kRing * (part_len(e) + 1) * 8);
   }
   if (G > 1 && G <= 1024 && e->W == 1 && e->mode >= GOSSIP_MODE_PUSH && e->mode <= GOSSIP_MODE_PUSHPULL &&
-      !(cfg->flags & (GOSSIP_FLAG_DIRECT | GOSSIP_FLAG_DENSE))) {
+      !(cfg->flags & (direct_flags | GOSSIP_FLAG_DENSE))) {
     e->sg = SxGeom{e->N, e->Nl, e->lo, e->nown, G, e->rank, e->k, e->R};
     if (!alloc(e->lf_mem, frontier_bytes(e->nown)) || !alloc(e->sx_mem, sx_bytes(e->sg))) return bail(GOSSIP_ENOMEM);
     frontier_carve(e->nown, e->lf_mem, &e->lf);
@@ -1980,7 +2008,7 @@ uint64_t gossip_partial_len(const gossip_engine_t* e) { return e ? part_len(e) :
 
 int gossip_exchange_buffers(gossip_engine_t* e, void** send, void** recv, uint64_t* send_bytes) {
   if (!e) return GOSSIP_EINVAL;
-  if (e->mode == GOSSIP_MODE_FLOOD && !e->has_topo) return e->fail(GOSSIP_ESTATE, "FLOOD needs a topology");
+  if (int rc = need_topo(e)) return rc;
   if (int rc = set_dev(e)) return rc;
   // the state all-gather rounds' slab is placed before the first collective starts: trials
   // timed while the all-gather runs would read a half-written image under link traffic (a
@@ -2041,7 +2069,7 @@ int pub_ready(gossip_engine* e, bool collect, bool count = true) {
 int gossip_round_compute(gossip_engine_t* e, uint64_t* partial) {
   if (!e || !partial) return GOSSIP_EINVAL;
   if (e->aex) return e->fail(GOSSIP_ESTATE, "sharded ANTIENTROPY rounds run through the gossip_ae_* calls");
-  if (e->mode == GOSSIP_MODE_FLOOD && !e->has_topo) return e->fail(GOSSIP_ESTATE, "FLOOD needs a topology");
+  if (int rc = need_topo(e)) return rc;
   if (int rc = set_dev(e)) return rc;
   if (int rc = compute_round(e, current_image(e))) return rc;
   if (e->mode != GOSSIP_MODE_ANTIENTROPY) {  // (ae_round read partial and aux back already)
@@ -2060,7 +2088,7 @@ int gossip_round_compute_dev(gossip_engine_t* e, const uint64_t** partial) {
   if (!e || !partial) return GOSSIP_EINVAL;
   if (e->aex || e->mode == GOSSIP_MODE_ANTIENTROPY)
     return e->fail(GOSSIP_ENOTSUP, "ANTIENTROPY partials are finished on the host: gossip_round_compute");
-  if (e->mode == GOSSIP_MODE_FLOOD && !e->has_topo) return e->fail(GOSSIP_ESTATE, "FLOOD needs a topology");
+  if (int rc = need_topo(e)) return rc;
   if (int rc = set_dev(e)) return rc;
   if (int rc = pub_alloc(e)) return rc;
   if (int rc = compute_round(e, current_image(e))) return rc;
@@ -2075,7 +2103,7 @@ int gossip_round_commit(gossip_engine_t* e, const uint64_t* total, gossip_round_
   if (!e || !total) return GOSSIP_EINVAL;
   if (e->stall_d) {  // stall streaks after round t, every shard over all N nodes
     if (int rc = set_dev(e)) return rc;
-    HIP_OK(e, launch_stall_update(e->stall_d, e->N, e->k, e->t, e->key0, e->key1, e->fa, e->stream));
+    if (int rc = stall_after_round(e, e->t)) return rc;
   }
   if (!e->last_sparse && !e->rep_planned) rotate(e);  // sparse and replicated rounds update S in place
   e->rep_img_ok = e->rep_planned;  // a replicated round leaves S_{t+1} of every node in the image
@@ -2728,14 +2756,14 @@ int gossip_step(gossip_engine_t* e, uint32_t max_rounds, gossip_round_stats_t* s
   if (rounds_done) *rounds_done = 0;
   if (e->G != 1) {  // sharded rounds over the engine's own collectives
     if (!e->tr) return e->fail(GOSSIP_ESTATE, "G > 1: gossip_comm_init_rank first (or run the round_* calls)");
-    if (e->mode == GOSSIP_MODE_FLOOD && !e->has_topo) return e->fail(GOSSIP_ESTATE, "FLOOD needs a topology");
+    if (int rc = need_topo(e)) return rc;
     std::string err;
     const DrivenScope ds({e});
     const int rc = sharded_step({e}, e->tr, max_rounds, stats, infected, rounds_done, &err);
     if (rc) e->err = err;
     return rc;
   }
-  if (e->mode == GOSSIP_MODE_FLOOD && !e->has_topo) return e->fail(GOSSIP_ESTATE, "FLOOD needs a topology");
+  if (int rc = need_topo(e)) return rc;
   if (int rc = set_dev(e)) return rc;
   if (e->binned) return step_planned(e, max_rounds, stats, infected, rounds_done);
   if (e->mode == GOSSIP_MODE_ANTIENTROPY && !e->aex) return step_ae(e, max_rounds, stats, infected, rounds_done);
@@ -2862,6 +2890,12 @@ uint32_t gossip_round_index(const gossip_engine_t* e) { return e ? e->t : 0; }
 uint32_t gossip_peer(uint64_t seed, uint64_t n_nodes, uint32_t node, uint32_t round, uint32_t j) {
   const u32x4 x = philox4x32_10(u32x4{node, round, 0u, j >> 2}, (uint32_t)seed, (uint32_t)(seed >> 32));
   return peer_from_word(lane_of(x, j & 3u), n_nodes - 1, node);
+}
+
+uint32_t gossip_topo_peer_index(uint64_t seed, uint32_t degree, uint32_t node, uint32_t round, uint32_t j) {
+  if (degree == 0) return 0;
+  const u32x4 x = philox4x32_10(u32x4{node, round, 0u, j >> 2}, (uint32_t)seed, (uint32_t)(seed >> 32));
+  return topo_index_from_word(lane_of(x, j & 3u), degree);
 }
 
 int gossip_philox_device(gossip_engine_t* e, const uint32_t* ctr4, const uint32_t* key2, uint32_t* out4, uint32_t n) {

@@ -16,6 +16,7 @@ FLAG_DIRECT = 1 << 2
 FLAG_DENSE = 1 << 3
 FLAG_SHARD_DIRECT = 1 << 4
 FLAG_AE_DIRECT_SCAN = 1 << 5
+FLAG_TOPO_PEERS = 1 << 6  # random modes: peers drawn from the node's topology row
 
 ABI_VERSION = 10  # include/gossip.h GOSSIP_ABI_VERSION (v10: gossip_round_wall)
 
@@ -118,6 +119,7 @@ SIGNATURES = [
     ("state_hash", C.c_int, [P, U64P]),
     ("round_index", C.c_uint32, [P]),
     ("peer", C.c_uint32, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("topo_peer_index", C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("philox_device", C.c_int, [P, U32P, U32P, U32P, C.c_uint32]),
     ("kernel_time", C.c_int, [P, C.c_uint32, C.POINTER(C.c_double), U64P]),
     ("reset_timing", C.c_int, [P]),

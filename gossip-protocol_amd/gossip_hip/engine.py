@@ -606,3 +606,9 @@ class Group:
 def peer(seed: int, n_nodes: int, node: int, round_: int, j: int) -> int:
     """p_j(node, round) as the kernels draw it (host copy of the device function)."""
     return int(load_library().gossip_peer(seed, n_nodes, node, round_, j))
+
+
+def topo_peer_index(seed: int, degree: int, node: int, round_: int, j: int) -> int:
+    """The row index i_j that `node` draws in `round_` for its j-th peer under FLAG_TOPO_PEERS
+    (DESIGN.md §2.10), as the kernels compute it; 0 for an empty row."""
+    return int(load_library().gossip_topo_peer_index(seed, degree, node, round_, j))

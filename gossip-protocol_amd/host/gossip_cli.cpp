@@ -3,8 +3,11 @@
 // with cgo: INTEGRATION.md) drives the engine.  Runs full disseminations and
 // prints one JSON line per run.
 //
-//   gossip_cli [--nodes N] [--rumors R] [--mode push|pull|pushpull|flood-grid]
+//   gossip_cli [--nodes N] [--rumors R] [--mode push|pull|pushpull|flood-grid|MODE-grid]
 //              [--fanout K] [--seed S] [--runs M] [--hash]
+//              [--topo-peers]   with push-grid, pull-grid or pushpull-grid: random gossip over
+//                               the grid, K of a node's grid neighbours per round
+//                               (GOSSIP_FLAG_TOPO_PEERS); prints the messages sent
 //              [--shards G [--devices d0,d1,...]]   G shards in this process, every round
 //                                                   driven by the library (gossip_group_*:
 //                                                   RCCL over distinct devices, else copies)
@@ -33,7 +36,7 @@ int main(int argc, char** argv) {
   uint32_t rumors = 1, fanout = 3, runs = 3, shards = 1;
   std::vector<int32_t> devices;
   std::string mode = "push";
-  bool hash = false;
+  bool hash = false, topo_peers = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
@@ -44,6 +47,7 @@ int main(int argc, char** argv) {
     else if (a == "--seed") seed = std::strtoull(next(), nullptr, 0);
     else if (a == "--runs") runs = (uint32_t)std::strtoul(next(), nullptr, 0);
     else if (a == "--hash") hash = true;
+    else if (a == "--topo-peers") topo_peers = true;
     else if (a == "--shards") shards = (uint32_t)std::strtoul(next(), nullptr, 0);
     else if (a == "--devices") {
       for (char* p = next(); *p;) {
@@ -64,13 +68,23 @@ int main(int argc, char** argv) {
   cfg.seed = seed;
   cfg.device = -1;
   cfg.shard_count = 1;
-  cfg.flags = hash ? GOSSIP_FLAG_HASH : 0;
-  const bool grid = mode == "flood-grid";
-  cfg.mode = mode == "push" ? GOSSIP_MODE_PUSH : mode == "pull" ? GOSSIP_MODE_PULL
-           : mode == "pushpull" ? GOSSIP_MODE_PUSHPULL : GOSSIP_MODE_FLOOD;
+  cfg.flags = (hash ? GOSSIP_FLAG_HASH : 0) | (topo_peers ? GOSSIP_FLAG_TOPO_PEERS : 0);
+  const size_t dash = mode.rfind("-grid");
+  const bool grid = dash != std::string::npos && dash + 5 == mode.size();
+  const std::string base = grid ? mode.substr(0, dash) : mode;
+  if (base != "push" && base != "pull" && base != "pushpull" && !(grid && base == "flood")) {
+    std::fprintf(stderr, "unknown mode %s\n", mode.c_str());
+    return 2;
+  }
+  if (topo_peers != (grid && base != "flood")) {
+    std::fprintf(stderr, "--topo-peers goes with push-grid, pull-grid or pushpull-grid (and they with it)\n");
+    return 2;
+  }
+  cfg.mode = base == "push" ? GOSSIP_MODE_PUSH : base == "pull" ? GOSSIP_MODE_PULL
+           : base == "pushpull" ? GOSSIP_MODE_PUSHPULL : GOSSIP_MODE_FLOOD;
   if (shards > 1) {  // the library runs every sharded round
     if (grid) {
-      std::fprintf(stderr, "--shards: random modes only\n");
+      std::fprintf(stderr, "--shards: random modes over all nodes only\n");
       return 2;
     }
     if (!devices.empty() && devices.size() != shards) {
@@ -132,10 +146,12 @@ int main(int argc, char** argv) {
     if (int rc = gossip_step(e, (uint32_t)st.size(), st.data(), nullptr, &done)) return die(e, "gossip_step", rc);
     const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     const gossip_round_stats_t& last = st[done ? done - 1 : 0];
+    uint64_t messages = 0;  // FLOOD and --topo-peers count them (0 for random gossip over all nodes)
+    for (uint32_t r = 0; r < done; ++r) messages += st[r].messages;
     std::printf("{\"run\":%u,\"mode\":\"%s\",\"nodes\":%llu,\"rumors\":%u,\"rounds\":%u,\"converged\":%u,"
-                "\"node_updates_per_s\":%.4e,\"seconds\":%.6f,\"state_hash\":\"0x%016llx\"}\n",
+                "\"messages\":%llu,\"node_updates_per_s\":%.4e,\"seconds\":%.6f,\"state_hash\":\"0x%016llx\"}\n",
                 run, mode.c_str(), (unsigned long long)nodes, rumors, done, last.converged,
-                (double)nodes * done / s, s, (unsigned long long)last.state_hash);
+                (unsigned long long)messages, (double)nodes * done / s, s, (unsigned long long)last.state_hash);
   }
   gossip_destroy(e);
   return 0;

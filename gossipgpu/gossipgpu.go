@@ -55,7 +55,8 @@ const (
 	AntiEntropy Mode = Mode(C.GOSSIP_MODE_ANTIENTROPY)
 )
 
-// Flags select optional outputs and A/B round paths (results never change).
+// Flags select optional outputs and A/B round paths (results never change), and with
+// FlagTopoPeers the peer source of the random modes (results do change: include/gossip.h).
 type Flags uint32
 
 const (
@@ -65,6 +66,9 @@ const (
 	FlagDense        Flags = Flags(C.GOSSIP_FLAG_DENSE)
 	FlagShardDirect  Flags = Flags(C.GOSSIP_FLAG_SHARD_DIRECT)
 	FlagAEDirectScan Flags = Flags(C.GOSSIP_FLAG_AE_DIRECT_SCAN)
+	// FlagTopoPeers: Push / Pull / PushPull draw each node's k peers from its topology row
+	// (SetTopology first), not from all N nodes; RoundStats.Messages counts the exchanges.
+	FlagTopoPeers Flags = Flags(C.GOSSIP_FLAG_TOPO_PEERS)
 )
 
 // Config mirrors gossip_config_t.  Probabilities are thresholds x / 2^32 (Threshold).
@@ -559,6 +563,12 @@ func (e *Engine) PhiloxDevice(ctr []uint32, key [2]uint32) ([]uint32, error) {
 // Peer is p_j(node, round) exactly as the kernels draw it.
 func Peer(seed, nodes uint64, node, round, j uint32) uint32 {
 	return uint32(C.gossip_peer(C.uint64_t(seed), C.uint64_t(nodes), C.uint32_t(node), C.uint32_t(round), C.uint32_t(j)))
+}
+
+// TopoPeerIndex is the index into a row of degree entries that node draws in round for its
+// j-th peer under FlagTopoPeers, exactly as the kernels compute it (0 for an empty row).
+func TopoPeerIndex(seed uint64, degree, node, round, j uint32) uint32 {
+	return uint32(C.gossip_topo_peer_index(C.uint64_t(seed), C.uint32_t(degree), C.uint32_t(node), C.uint32_t(round), C.uint32_t(j)))
 }
 
 // locked runs one cgo call under e.mu (one engine is not thread-safe, include/gossip.h).

@@ -68,8 +68,19 @@ enum gossip_flags {
                                    sparse (frontier) rounds — same results, for A/B checks */
   GOSSIP_FLAG_SHARD_DIRECT = 1u << 4,  /* sharded engines: dense rounds on the direct kernels instead
                                           of the binned push / pull passes — same results, A/B */
-  GOSSIP_FLAG_AE_DIRECT_SCAN = 1u << 5 /* ANTIENTROPY: sparse rounds probe the peers' bitmap words
+  GOSSIP_FLAG_AE_DIRECT_SCAN = 1u << 5, /* ANTIENTROPY: sparse rounds probe the peers' bitmap words
                                           directly instead of binning by tile — same results, A/B */
+  GOSSIP_FLAG_TOPO_PEERS = 1u << 6     /* PUSH / PULL / PUSHPULL: the k peers of node n are drawn from its
+                                          topology row (a sorted set, self-loops kept) instead of from all
+                                          N nodes: p_j = row_n[floor(x_j * deg(n) / 2^32)] over the Philox
+                                          words x_j of the uniform draw, with replacement; an empty row
+                                          initiates nothing.  Faults and stall_rounds
+                                          apply to these edges unchanged; stats.messages counts the
+                                          exchanges initiated.  gossip_step without a topology returns
+                                          GOSSIP_ESTATE; a new topology takes effect in the next round.
+                                          Such engines run the direct kernels (as GOSSIP_FLAG_DIRECT),
+                                          sharded ones through the state all-gather round.  With FLOOD or
+                                          ANTIENTROPY gossip_create returns GOSSIP_EINVAL */
 };
 
 typedef struct gossip_config {
@@ -106,7 +117,11 @@ typedef struct gossip_round_stats {
   uint64_t full_nodes;  /* nodes holding all R rumors                            */
   uint64_t alive_nodes; /* N, or the alive count after round t's churn (ANTIENTROPY) */
   uint64_t messages;    /* FLOOD: broadcast RPCs sent in round t;
-                           ANTIENTROPY: exchanges between two alive nodes           */
+                           ANTIENTROPY: exchanges between two alive nodes;
+                           GOSSIP_FLAG_TOPO_PEERS: exchanges initiated in round t, lost attempts
+                           included — k per node with a row that is not empty
+                           and not stalled (PUSH: and a rumor to send); other random-mode
+                           engines: 0                                               */
   uint64_t state_hash;  /* GOSSIP_FLAG_HASH: Σ mix64 over nonzero words, else 0   */
 } gossip_round_stats_t;
 
@@ -185,8 +200,10 @@ int gossip_set_stream(gossip_engine_t* eng, void* hip_stream);
  *                  row once fewer than 90 % of the nodes are stale (default), 0 gather them all */
 int gossip_set_param(gossip_engine_t* eng, const char* name, double value);
 
-/* FLOOD peer source: directed adjacency Topology[u] = col[row_ptr[u]..row_ptr[u+1]),
- * global node ids, n == N.  Copied; never retained.  Plain FLOOD reads each row as a set;
+/* Peer source of FLOOD and of the random modes created with GOSSIP_FLAG_TOPO_PEERS (other
+ * random-mode engines accept a topology and draw over all N nodes all the same): directed
+ * adjacency Topology[u] = col[row_ptr[u]..row_ptr[u+1]),
+ * global node ids, n == N.  Copied; never retained.  Plain FLOOD and the random modes read each row as a set;
  * an engine created with faults or stall_rounds keeps each row as listed (order and
  * repeats: the forwarding walk of main.go:72-87) and ends every walk (a
  * known divergence: the reference's in-flight goroutine keeps the row it read at main.go:72). */
@@ -271,6 +288,9 @@ uint32_t gossip_round_index(const gossip_engine_t* eng);
 
 /* Philox peer draw p_j(n, t) exactly as the kernels compute it (parity probe). */
 uint32_t gossip_peer(uint64_t seed, uint64_t n_nodes, uint32_t node, uint32_t round, uint32_t j);
+/* GOSSIP_FLAG_TOPO_PEERS: the index i_j into a row of `degree` entries that node draws in round
+ * for its j-th peer, exactly as the kernels compute it (host code, parity probe); 0 for degree 0. */
+uint32_t gossip_topo_peer_index(uint64_t seed, uint32_t degree, uint32_t node, uint32_t round, uint32_t j);
 
 /* Device-side Philox4x32-10 of n counters (known-answer tests): ctr4/out4 hold
  * 4*n words, key2 = 2 words. Runs on the engine's device. */
