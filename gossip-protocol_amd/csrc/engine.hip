@@ -22,6 +22,7 @@
 #include "binned.h"
 #include "devmem.h"
 #include "frontier.h"
+#include "plan.h"
 #include "sharded.h"
 #include "round.h"
 
@@ -183,17 +184,9 @@ struct gossip_engine {
   FrontierBufs fb{};
   DevBuf<uint8_t> fr_mem;
   bool fr_valid = false;          // partial_d holds the totals of S and the bitmaps are exact
-  double sparse_frac = 1.0 / 16;  // rare fraction at or below which a round runs sparse (sparse_frac_of)
-  bool sparse_frac_set = false;   // set by gossip_set_param (else the sharded defaults apply)
-  double filter_frac = 0.3;       // dense rounds filter edges by the peer's class above this empty / full fraction
-  bool filter_frac_set = false;   // else off past 2^25 nodes (filter_frac_of)
-  double xd_filter_frac = 0.6;    // exchange rounds likewise (their probe hits a G-shard class image: G = 8 sweep)
-  double alld_frac = 1.0 / 128;   // sparse rounds with k * rare >= alld_frac * N commit every group's D (sweep: profiles/r05_ad/)
-  bool sparse_direct = true;      // ... and with an empty majority take the pushes into empty peers in S (kSparseDirect)
-  // sparse rounds take the binned scan (frontier.hip K1a / K1b) once this share of peers would hit
-  // the LDS summary (param bin_scan_frac)
-  double bscan_frac = 0.6;
-  double mid_frac = 0.5;          // sparse rounds test peers in the mid-level summary once this share hits the LDS one
+  // the round planner's shape, knobs (gossip_set_param, gossip_set_faults) and state: plan.h
+  plan_cfg pl{};
+  bool sparse_direct = true;      // all-D sparse rounds with an empty majority take the pushes into empty peers in S (kSparseDirect)
   // pipelined rounds (binned engines): the host picks each round's path from the
   // totals it has read, predicted forward over the rounds still in flight, and
   // stays up to `ahead` rounds in front
@@ -226,36 +219,29 @@ struct gossip_engine {
   uint64_t sx_stride = 0;
   // exchange dense rounds (binned.h: XdGeom), buffers allocated at the first one
   bool xd = false, xd_planned = false;
-  uint32_t xd_shards = 6;  // gossip_set_param "xd_shards": G at which dense rounds become exchange rounds
   XdGeom xg{};
   XdBufs xb{};
   DevBuf<uint8_t> xd_smem, xd_rmem;
   uint64_t xd_rcap = 0, xd_nin = 0;  // xd_rcap: the items xd_rmem was carved for (xd_carve_recv)
   PinBuf<uint32_t> xd_cnt_h;  // [G]
-  uint32_t xd_filt = 0;          // this round's edge filter (dense_filter of the global totals)
+  uint32_t xd_filt = 0;          // this round's edge filter (plan_dense_filter of the global totals)
   bool xd_cls_ok = false;        // gossip_xd_classes handed out the own bitmaps for this round
   DevBuf<uint64_t> xd_cls;       // [G][2 * nwl] every shard's occupancy bitmaps of S_t (all-gather in place)
   DevBuf<uint8_t> xd_keep;       // [nown] per sender: the edges that survive the filter (count pass -> emit)
   // class-coded state exchange for dense image rounds (sharded.h cc_*), plan kind 4
   bool cc_planned = false;
-  double cc_frac = 0.75;
   // replicated dense rounds (plan kinds 5 / 6): every rank runs the one-GPU binned
   // round over the whole state image in place, so the next dense round needs no collective
   // before it (kind 6) — where the links cost more than the extra device time (G = 2 at 2^27)
-  int replicate = -1;           // gossip_set_param "replicate": -1 by the cost model, 0 never, 1 every dense round
-  bool rep_planned = false;     // this round is replicated
-  bool rep_img_ok = false;      // the image holds S_t of every node (the last round was replicated)
+  bool rep_planned = false;     // this round is replicated (pl.rep_img_ok: the last one was)
   BinGeom rbg{};
   BinBufs rbb{};
   DevBuf<uint8_t> rep_mem;      // the one-GPU record slab over all N nodes, at the first replicated round
   DevBuf<uint64_t> rep_part;    // that round's whole-image totals (scratch: the ranks report own-slice totals)
-  // gossip_set_param "link_gbps": sharded random-mode rounds pick sparse / dense by a per-rank
-  // cost model with a link term (shard_round_costs); 0 = the fixed sparse_frac thresholds
-  double link_gbps = 76.0;
   std::string model_plan;                // gossip_plan_model: this run's plan kinds, one letter per round
   double model_ms = 0, model_link_ms = 0;  // the modelled per-rank ms of the planned rounds since reset_timing
   uint64_t model_rounds = 0;
-  double plan_cost[2] = {};  // the last plan's modelled sparse / dense ms (tools/shard_probe.py)  // gossip_set_param "cc_frac": at most this global fraction of mixed nodes
+  double plan_cost[2] = {};  // the last plan's modelled sparse / dense ms (tools/shard_probe.py)
   DevBuf<uint64_t> cc_bits;     // [G][cc_slot_words] every shard's bitmaps + prefix (all-gather in place)
   DevBuf<uint64_t> cc_vals;     // [G][stride] the shards' mixed words
   uint64_t cc_stride = 0;
@@ -646,178 +632,20 @@ int prepare_planned(gossip_engine* e) {
   return GOSSIP_OK;
 }
 
-// Totals the path choice needs: full and nonzero counts, per-rumor infected.
-struct Est {
-  double full = 0, nz = 0;
-  std::vector<double> inf;
-};
-
-Est est_of(const gossip_engine* e, const uint64_t* tot) {
-  Est x;
-  x.full = (double)tot[0];
-  x.nz = (double)tot[4 + e->R];
-  x.inf.assign(tot + 4, tot + 4 + e->R);
-  return x;
-}
-
-// One round of the mean-field model of the random modes, per rumor: a node
-// misses rumor r after the round iff it held no copy, none of its k pulls hit a
-// holder (u^k) and no holder pushed to it (e^{-k(1-u)}).  Only steers the path
-// choice, never a result.
-Est predict(const gossip_engine* e, const Est& x) {
-  Est y;
-  // lost edges (§2.8) thin the fanout; a partition keeps ~1/P of the peers
-  const double keep = (1.0 - (double)e->fa.loss / 4294967296.0) * (e->fa.parts > 1 ? 1.0 / e->fa.parts : 1.0);
-  const double N = (double)e->N, k = (double)e->k * keep;
-  const bool push = e->mode == GOSSIP_MODE_PUSH || e->mode == GOSSIP_MODE_PUSHPULL;
-  const bool pull = e->mode == GOSSIP_MODE_PULL || e->mode == GOSSIP_MODE_PUSHPULL;
-  double all_miss = 1.0, all_hit = 1.0;
-  y.inf.resize(x.inf.size());
-  for (size_t r = 0; r < x.inf.size(); ++r) {
-    const double u = 1.0 - x.inf[r] / N;
-    double v = u;
-    if (pull) v *= std::pow(u, k);
-    if (push) v *= std::exp(-k * (1.0 - u));
-    y.inf[r] = (1.0 - v) * N;
-    all_miss *= v;
-    all_hit *= 1.0 - v;
-  }
-  y.nz = N * (1.0 - all_miss);
-  y.full = N * all_hit;
-  return y;
-}
-
-// the sparse-round threshold: gossip_set_param's, else the default of the engine's dense
-// round kind — a sharded dense round that all-gathers the state costs more than an
-// exchange round, so sparse rounds pay off up to a larger rare fraction before it
-// (tools/shard_probe.py sweeps, profiles/r02_xd)
-double sparse_frac_of(const gossip_engine* e) {
-  if (e->sparse_frac_set || !e->sx) return e->sparse_frac;
-  // before exchange rounds: 1/25 (a round with ~5 % rare nodes is cheaper as a class-filtered
-  // exchange round, profiles/r02_xdfilt/); before state all-gathers: 1/4
-  return e->xd && e->xd_shards && e->G >= e->xd_shards ? 0.04 : 0.25;
-}
-
-// Per-rank cost model of one sharded round of the random modes, in ms: device time from the
-// measured rates plus link time = the bytes the rank sends over its links /
-// (link_gbps x the G - 1 links it uses, at most 7).  Only steers the plan (every kind computes
-// the same bits).  Device rates: a sparse round costs 2.3 ps per own node (the Philox floor; round
-// 0 at 2^27 on one GPU: 311 us) plus up to 70 ps per own node as the rare share r grows, x (1 -
-// e^(-r / 0.05)) (the summaries saturate: G = 2 x 2^26 at r = 3.7 / 19 / 25 %: 2.41 / 5.0 / 4.83 ms,
-// profiles/r05_shard/probe_G2_fixed.txt); a dense round on the state image 7.3 ps per image node + 47 ps per own node (N = 2 / 4
-// ranks x 2^26 / 2^25: 4.14 / 2.56 ms, profiles/r04_ad/); an exchange round 67 ps per own node
-// (G = 8 x 2^24: 1.13 ms, profiles/r02_xd/).  Link bytes per rank: sparse = the rare-list
-// all-gather (16 B per rare node of the shard to each other shard) + the off-shard pushes
-// (16 B items, ~k per rare node); state all-gather = 8 B per own node to each other shard
-// (class-coded: its bitmaps + prefixes, 20 B per 64 nodes, + 8 B per mixed node); exchange =
-// 40 (G - 1) / G B per own node (12-B items out, 8-B replies back, k = 2).
-struct ShardCosts {
-  double sparse, dense;            // modelled ms per rank: device + link
-  double sparse_link, dense_link;  // their link parts
-  bool dense_xd, dense_cc;
-  // a replicated dense round (kinds 5 / 6): device time of the one-GPU round over
-  // all N nodes (5.1 ms at 2^27 on MI355X: 3.8e-8 ms per node) plus the own-slice totals, and the
-  // state all-gather when the image is not whole yet (kind 5)
-  double rep, rep_link;
-  bool rep_ok;
-};
-uint32_t dense_filter(const gossip_engine* e, const Est& x, double frac);
-
-ShardCosts shard_round_costs(const gossip_engine* e, const Est& x) {
-  // (Nl, not the own count: every rank must reach the same plan, also with ragged shards)
-  const double N = (double)e->N, G = (double)e->G, Nl = (double)e->Nl, k = (double)e->k;
-  const double rare = std::min(x.nz, N - x.full), rare_own = rare / G;
-  const double bw = e->link_gbps * 1e6 * std::min(G - 1.0, 7.0);  // bytes per ms
-  ShardCosts c{};
-  c.sparse_link = (16.0 * rare_own * (G - 1.0) + 16.0 * k * rare_own * (G - 1.0) / G) / bw;
-  c.sparse = Nl * (2.3e-9 + 7.0e-8 * (1.0 - std::exp(-rare / N / 0.05))) + c.sparse_link;
-  c.dense_xd = e->xd && e->xd_shards && e->G >= e->xd_shards;
-  const double mixed = std::max(0.0, x.nz - x.full);
-  c.dense_cc = !c.dense_xd && e->cc_frac > 0 && mixed / N <= e->cc_frac;
-  if (c.dense_xd) {
-    // items per own sender edge that survive the class filter (gossip_xd_classes, dense_filter of
-    // these totals): a pull-only edge (empty sender) into an empty peer and a push-only one (full
-    // sender) into a full peer are never sent.  Device time fitted on the G = 8 probe (unfiltered
-    // 1.15 ms, filtered at 34 % kept 0.93 ms per 2^24-node rank, profiles/r05_probes/); round 4's
-    // model priced every round unfiltered and planned the two filtered rounds sparse (1.6-1.7 ms)
-    const uint32_t filt = e->k <= 8 ? dense_filter(e, x, e->xd_filter_frac) : 0u;
-    const double ef = 1.0 - x.nz / N, ff = x.full / N, mf = std::max(0.0, 1.0 - ef - ff);
-    const double kept = mf + ef * ((filt & 1u) ? 1.0 - ef : 1.0) + ff * ((filt & 2u) ? 1.0 - ff : 1.0);
-    c.dense_link = 40.0 * (G - 1.0) / G * Nl * kept / bw;
-    c.dense = Nl * (4.85e-8 + 2.0e-8 * kept) + c.dense_link;
-  } else {
-    const double slice = c.dense_cc ? 20.0 / 64.0 * Nl + 8.0 * mixed / G : 8.0 * Nl;
-    c.dense_link = slice * (G - 1.0) / bw;
-    c.dense = 7.3e-9 * N + 4.7e-8 * Nl + c.dense_link;
-  }
-  c.rep_ok = e->replicate != 0 && e->sx && bin_path_ok(e->N, e->k, 1, 1);
-  // entering gathers the image class-coded where the dense round would (kind 7), else whole (5)
-  const double cc_slice = 20.0 / 64.0 * Nl + 8.0 * mixed / G;
-  c.rep_link = e->rep_img_ok ? 0.0 : (c.dense_cc ? cc_slice : 8.0 * Nl) * (G - 1.0) / bw;
-  c.rep = 3.8e-8 * N + 1.5e-9 * Nl + c.rep_link;
-  return c;
-}
-
-// What replicating saves over the dense rounds after this one (kind 6 instead of a sharded dense
-// round each), as far as the mean-field predictor sees them: up to 8 rounds, until one that the
-// model would run sparse.  Only steers the plan.
-double rep_gain_ahead(const gossip_engine* e, Est x) {
-  double gain = 0.0;
-  for (int i = 0; i < 8; ++i) {
-    x = predict(e, x);
-    const ShardCosts c = shard_round_costs(e, x);
-    const double rep6 = c.rep - c.rep_link;
-    if (c.sparse < std::min(c.dense, rep6)) break;  // the dense phase ends
-    gain += std::max(0.0, c.dense - rep6);
-  }
-  return gain;
-}
-
-// sparse when the smaller rare class is at most sparse_frac * N; maj = which
-// class is rare; all_d once the rare ends' pushes (~k per rare node) reach
-// alld_frac * N (launch_frontier_round)
-bool choose_sparse(const gossip_engine* e, const Est& x, uint32_t* maj, bool* all_d) {
-  if (!e->frontier && !e->sx) return false;
-  const double lo = x.nz, hi = (double)e->N - x.full, rare = std::min(lo, hi);
-  *maj = hi < lo ? 1u : 0u;
-  *all_d = rare * (double)e->k >= e->alld_frac * (double)e->N;
-  return rare <= sparse_frac_of(e) * (double)e->N;
-}
-
 // the binned sparse scan: once the LDS summary (g nodes per bit) would have a bit set under
-// 1 - (1 - r)^g >= bscan_frac of the peers it filters too little, and binning every edge by peer
+// plan_bscan_hit >= bscan_frac of the peers it filters too little, and binning every edge by peer
 // tile costs less than probing the mid-level summary and the exact bitmap per edge (DESIGN.md
 // §3.3).  Its records and run table live in the dense round's record slab.
-bool bscan_round(const gossip_engine* e, const Est& x, uint32_t maj) {
-  if (!e->binned || !e->frontier || !bs_path_ok(e->N, e->k) || e->bscan_frac > 1.0) return false;
+bool bscan_round(const gossip_engine* e, const plan_est& x, uint32_t maj) {
+  if (!e->binned || !e->frontier || !bs_path_ok(e->N, e->k) || e->pl.bscan_frac > 1.0) return false;
   const size_t recs = (size_t)e->bg.nt_s * e->bg.rp;
   if (bs_rec_bytes(e->N, e->k) > recs * 8 || bs_tab_bytes(e->N) > recs * 8) return false;
-  if (e->bscan_frac <= 0.0) return true;
+  if (e->pl.bscan_frac <= 0.0) return true;
   // by default only where the LDS summary is coarse (g >= 64 nodes per bit: past 2^25 nodes, where
   // the mid-level summary exists); at 2^24 the one heavy sparse round it took ran 590 us and the
   // step's sparse rounds 1.10 -> 1.44 ms (K1b has too few regions per tile to fill its waves)
   if (!e->fb.summ2) return false;
-  const double N = (double)e->N, rare = maj ? N - x.full : x.nz;
-  const double g = (double)(1u << e->fb.glog);
-  return 1.0 - std::pow(1.0 - std::min(std::max(rare / N, 0.0), 1.0), g) >= e->bscan_frac;
-}
-
-// dense rounds: probe the peer's class in emit when many edges would move
-// nothing (pulls from empty peers early in a run, pushes into full peers late)
-uint32_t dense_filter(const gossip_engine* e, const Est& x, double frac) {
-  const double N = (double)e->N, empty = 1.0 - x.nz / N, full = x.full / N;
-  const bool pull = e->mode == GOSSIP_MODE_PULL || e->mode == GOSSIP_MODE_PUSHPULL;
-  const bool push = e->mode == GOSSIP_MODE_PUSH || e->mode == GOSSIP_MODE_PUSHPULL;
-  return (pull && empty > frac ? 1u : 0u) | (push && full > frac ? 2u : 0u);
-}
-
-// the one-shard dense filter's threshold: gossip_set_param's, else 0.3 while the occupancy
-// bitmaps (N/8 bytes each) fit an XCD's 4 MiB L2; past that every probe is a 64-B fetch from
-// the MALL or HBM and the probes cost more than the edges they drop (2^27 nodes: emit
-// 2.3 -> 6.3 ms, serve + apply -1.6 ms; profiles/r03_a/rounds.txt)
-double filter_frac_of(const gossip_engine* e) {
-  if (e->filter_frac_set) return e->filter_frac;
-  return e->N <= (1ull << 25) ? e->filter_frac : 2.0;
+  return plan_bscan_hit(&e->pl, &x, maj) >= e->pl.bscan_frac;
 }
 
 RoundSync ring_sync(gossip_engine* e, uint32_t slot) {
@@ -858,7 +686,7 @@ int launch_round_path(gossip_engine* e, uint32_t t, bool sparse, uint32_t maj, b
   // costs more than the exact probes it saves (2^27 nodes: rounds at 1-17 % LDS hits +50..130 us,
   // at 61 % -920 us; profiles/r03_mid).  The kernels decide from the exact rare count.
   FrontierBufs fb = e->fb;
-  fb.mid_frac = (float)e->mid_frac;
+  fb.mid_frac = (float)e->pl.mid_frac;
   if (sparse && bscan) {  // (the slab pointers change when placement re-carves it)
     fb.brec = (uint32_t*)e->bb.resp;
     fb.btab = (uint16_t*)(e->bb.prec ? (void*)e->bb.prec : (void*)e->bb.vals);
@@ -920,7 +748,7 @@ int step_planned(gossip_engine* e, uint32_t max_rounds, gossip_round_stats_t* st
   if (int rc = prepare_planned(e)) return rc;
   std::vector<uint64_t> t0tot;
   if (int rc = read_totals(e, &t0tot)) return rc;
-  Est base = est_of(e, t0tot.data());
+  plan_est base = plan_est_of(&e->pl, t0tot.data());
   const size_t pl = part_len(e);
   const uint32_t t0 = e->t;
   std::vector<uint64_t> want(kRing, 0);
@@ -933,12 +761,12 @@ int step_planned(gossip_engine* e, uint32_t max_rounds, gossip_round_stats_t* st
   if (e->timing) HIP_OK(e, hipEventRecord(e->ev[0][0], e->stream));
   while (done < max_rounds) {
     while (!stop && launched < max_rounds && launched - done < ahead) {
-      Est x = base;
-      for (uint32_t i = done; i < launched; ++i) x = predict(e, x);
+      plan_est x = base;
+      for (uint32_t i = done; i < launched; ++i) x = plan_predict(&e->pl, &x);
       uint32_t maj = 0;
-      bool all_d = false;
-      const bool sparse = choose_sparse(e, x, &maj, &all_d);
-      const uint32_t filt = dense_filter(e, x, filter_frac_of(e));
+      int all_d = 0;
+      const bool sparse = plan_choose_sparse(&e->pl, &x, &maj, &all_d);
+      const uint32_t filt = plan_dense_filter(&e->pl, &x, plan_filter_frac(&e->pl));
       const uint32_t slot = launched % kRing;
       const RoundSync rs = ring_sync(e, slot);
       want[slot] = rs.seq;
@@ -960,7 +788,7 @@ int step_planned(gossip_engine* e, uint32_t max_rounds, gossip_round_stats_t* st
     st.state_hash = (e->cfg.flags & GOSSIP_FLAG_HASH) ? tot[3] : 0;
     if (stats) stats[done] = st;
     if (infected) std::memcpy(infected + (size_t)done * e->R, tot + 4, (size_t)e->R * 8);
-    base = est_of(e, tot);
+    base = plan_est_of(&e->pl, tot);
     ++done;
     if (st.converged) stop = true;
     if (stop) break;
@@ -1326,10 +1154,10 @@ int compute_round(gossip_engine* e, const uint64_t* gathered) {
     std::vector<uint64_t> tot;
     if ((rc = read_totals(e, &tot))) return rc;
     uint32_t maj = 0;
-    bool all_d = false;
-    const Est x = est_of(e, tot.data());
-    const bool sparse = choose_sparse(e, x, &maj, &all_d);
-    const uint32_t filt = dense_filter(e, x, filter_frac_of(e));
+    int all_d = 0;
+    const plan_est x = plan_est_of(&e->pl, tot.data());
+    const bool sparse = plan_choose_sparse(&e->pl, &x, &maj, &all_d);
+    const uint32_t filt = plan_dense_filter(&e->pl, &x, plan_filter_frac(&e->pl));
     if ((rc = timer_begin(e, 0))) return rc;
     if ((rc = launch_round_path(e, e->t, sparse, maj, all_d, filt,
                                 ring_sync(e, 0), -1, sparse && bscan_round(e, x, maj))))
@@ -1559,6 +1387,9 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
   e->key0 = (uint32_t)cfg->seed;
   e->key1 = (uint32_t)(cfg->seed >> 32);
   e->fa = Faults{cfg->edge_loss, cfg->partitions, cfg->n_nodes};
+  plan_defaults(&e->pl);
+  e->pl.N = e->N, e->pl.Nl = e->Nl, e->pl.G = G, e->pl.k = e->k, e->pl.R = e->R, e->pl.mode = e->mode;
+  e->pl.edge_loss = cfg->edge_loss, e->pl.partitions = cfg->partitions;
   e->timing = (cfg->flags & GOSSIP_FLAG_TIMING) != 0;
   e->flood_edges = e->mode == GOSSIP_MODE_FLOOD && faulty;
   e->topo_peers = (cfg->flags & GOSSIP_FLAG_TOPO_PEERS) != 0;
@@ -1722,8 +1553,14 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
       }
       e->xd = true;
     }
-    // sharded sparse rounds pay off up to a larger rare fraction than on one GPU: sparse_frac_of
   }
+  // what the planner may choose from; the rare summaries (frontier_carve, sx_carve) by N alone
+  e->pl.sharded = e->sx;
+  e->pl.can_sparse = e->frontier || e->sx;
+  e->pl.can_xd = e->xd;
+  e->pl.can_rep = e->sx && bin_path_ok(e->N, e->k, 1, 1);
+  e->pl.glog = frontier_glog(e->N);
+  e->pl.has_mid = frontier_summ2_words(e->N) != 0;
   if (e->partial_h.alloc(part_len(e) + 8) != hipSuccess) {
     e->err = "hipHostMalloc failed";
     return bail(GOSSIP_ENOMEM);
@@ -1778,10 +1615,10 @@ int gossip_set_param(gossip_engine_t* e, const char* name, double v) {
   if (!e || !name) return GOSSIP_EINVAL;
   const std::string n(name);
   if (n == "sparse_frac") {
-    e->sparse_frac = v;
-    e->sparse_frac_set = true;
+    e->pl.sparse_frac = v;
+    e->pl.sparse_frac_set = 1;
   } else if (n == "alld_frac") {
-    e->alld_frac = v;
+    e->pl.alld_frac = v;
   } else if (n == "sparse_direct") {
     e->sparse_direct = v != 0;
   } else if (n == "ae_ahead") {
@@ -1800,31 +1637,31 @@ int gossip_set_param(gossip_engine_t* e, const char* name, double v) {
     e->place_tries = (uint32_t)v;
   } else if (n == "link_gbps") {
     if (v < 0) return e->fail(GOSSIP_EINVAL, "link_gbps must be >= 0 (0 = fixed sparse_frac thresholds)");
-    e->link_gbps = v;
+    e->pl.link_gbps = v;
   } else if (n == "rccl_dev_collectives") {
     e->rccl_dev = v != 0;
   } else if (n == "bin_scan_frac") {
-    e->bscan_frac = v;
+    e->pl.bscan_frac = v;
   } else if (n == "mid_frac") {
-    e->mid_frac = v;
+    e->pl.mid_frac = v;
   } else if (n == "scan_queue") {
     e->fb.scan_q = e->lf.scan_q = v != 0 ? 1u : 0u;
   } else if (n == "filter_frac") {
-    e->filter_frac = v;
-    e->filter_frac_set = true;
+    e->pl.filter_frac = v;
+    e->pl.filter_frac_set = 1;
   } else if (n == "xd_filter_frac") {
-    e->xd_filter_frac = v;
+    e->pl.xd_filter_frac = v;
   } else if (n == "ahead") {
     if (v < 1 || v > kRing - 1) return e->fail(GOSSIP_EINVAL, "ahead must be in [1, %u]", kRing - 1);
     e->ahead = (uint32_t)v;
   } else if (n == "replicate") {  // < 0: by the cost model, 0: never, > 0: every dense round
-    e->replicate = v < 0 ? -1 : v > 0 ? 1 : 0;
+    e->pl.replicate = v < 0 ? -1 : v > 0 ? 1 : 0;
   } else if (n == "cc_frac") {
     if (v < 0 || v > 1) return e->fail(GOSSIP_EINVAL, "cc_frac must be in [0, 1] (0 = never)");
-    e->cc_frac = v;
+    e->pl.cc_frac = v;
   } else if (n == "xd_shards") {
     if (v < 0 || v > 1024) return e->fail(GOSSIP_EINVAL, "xd_shards must be in [0, 1024] (0 = never)");
-    e->xd_shards = (uint32_t)v;
+    e->pl.xd_shards = (uint32_t)v;
   } else if (n == "ae_sparse") {
     if (v != -1 && v != 0 && v != 1) return e->fail(GOSSIP_EINVAL, "ae_sparse must be -1, 0 or 1");
     e->ae_force = (int)v;
@@ -1940,7 +1777,8 @@ int gossip_reset(gossip_engine_t* e) {
   e->sx_valid = e->gtot_valid = e->last_sparse = false;
   // a dense_prepare or sparse plan of the old state must not leak into the next round
   e->sb_pre = e->ev_pre_pending = e->sx_planned = e->xd_planned = e->cc_planned = false;
-  e->rep_planned = e->rep_img_ok = false;
+  e->rep_planned = false;
+  e->pl.rep_img_ok = 0;
   if (e->frontier) {  // all-zero state: zero totals, empty bitmaps (D and its dirty flags are zero between rounds)
     const size_t nwb = (e->N + 63) / 64 * 8;
     HIP_OK(e, hipMemsetAsync(e->fb.nzb, 0, nwb, e->stream));
@@ -1975,7 +1813,8 @@ int gossip_inject(gossip_engine_t* e, uint64_t node, uint32_t rumor) {
   }
   HIP_OK(e, launch_inject(e->S, e->Nl, e->lo, e->hi, e->N, e->R, e->key0, e->key1, (int64_t)node, rumor, e->stream,
                           e->flood_edges ? &e->fw : nullptr));
-  e->fr_valid = e->sx_valid = e->gtot_valid = e->rep_img_ok = false;
+  e->fr_valid = e->sx_valid = e->gtot_valid = false;
+  e->pl.rep_img_ok = 0;
   return GOSSIP_OK;
 }
 
@@ -2000,7 +1839,8 @@ int gossip_inject_random(gossip_engine_t* e) {
   }
   HIP_OK(e, launch_inject(e->S, e->Nl, e->lo, e->hi, e->N, e->R, e->key0, e->key1, -1, 0, e->stream,
                           e->flood_edges ? &e->fw : nullptr));
-  e->fr_valid = e->sx_valid = e->gtot_valid = e->rep_img_ok = false;
+  e->fr_valid = e->sx_valid = e->gtot_valid = false;
+  e->pl.rep_img_ok = 0;
   return GOSSIP_OK;
 }
 
@@ -2106,7 +1946,7 @@ int gossip_round_commit(gossip_engine_t* e, const uint64_t* total, gossip_round_
     if (int rc = stall_after_round(e, e->t)) return rc;
   }
   if (!e->last_sparse && !e->rep_planned) rotate(e);  // sparse and replicated rounds update S in place
-  e->rep_img_ok = e->rep_planned;  // a replicated round leaves S_{t+1} of every node in the image
+  e->pl.rep_img_ok = e->rep_planned;  // a replicated round leaves S_{t+1} of every node in the image
   e->rep_planned = false;
   if (e->aex) {  // V = S_{t+1}, Vn = S_t, aex_dirty = the rows where they differ
     e->aex_patch_ok = e->aex_round_done;
@@ -2184,52 +2024,22 @@ int gossip_sharded_plan(gossip_engine_t* e, const uint64_t* total, int32_t* kind
     *kind = -1;
     return GOSSIP_OK;
   }
-  uint32_t maj = 0;
-  bool all_d = false;
-  e->sx_planned = choose_sparse(e, est_of(e, e->gtot.data()), &maj, &all_d);
-  // (link_gbps 0: priced at the default rate, for gossip_plan_model only)
-  const ShardCosts c = shard_round_costs(e, est_of(e, e->gtot.data()));
-  const bool model = !e->sparse_frac_set && e->link_gbps > 0;
-  // replicated dense rounds: forced (param replicate 1), or by the model: with a whole image
-  // (kind 6) while one costs less than the sharded dense round; entering (kind 5: the all-gather
-  // plus the whole round) where what it costs over the sharded round is won back over the dense
-  // rounds the mean-field predictor (§3.4) sees ahead.  The model's per-node fits come from
-  // 2^24-2^27-node runs: below 2^22 nodes it replicates only when forced
-  const double rep6 = c.rep - c.rep_link;
-  bool rep_auto = e->replicate < 0 && model && e->N >= (1ull << 22) && rep6 < c.dense;
-  if (rep_auto && !e->rep_img_ok) rep_auto = c.rep - c.dense < rep_gain_ahead(e, est_of(e, e->gtot.data()));
-  const bool rep_any = c.rep_ok && (e->replicate == 1 || rep_auto);
-  if (model)  // the link-aware cost model decides instead
-    e->sx_planned = c.sparse < (rep_any ? std::min(c.dense, c.rep) : c.dense);
-  e->rep_planned = !e->sx_planned && rep_any;
-  e->plan_cost[0] = c.sparse;
-  e->plan_cost[1] = c.dense;
-  e->sx_maj = maj;
-  e->sx_alld = all_d;
-  {  // the mid-level summary of the global rare bitmap (choose_sparse's rule, sharded summary)
-    const Est x = est_of(e, e->gtot.data());
-    const double r = std::min(1.0, std::min(x.nz, (double)e->N - x.full) / (double)e->N);
-    e->sx_mid = e->sb.gsum.summ2 && 1.0 - std::pow(1.0 - r, (double)(1u << e->sb.gsum.glog)) >= e->mid_frac;
-  }
-  e->xd_planned = !e->sx_planned && !e->rep_planned && e->xd && e->xd_shards && e->G >= e->xd_shards;
-  // exchange rounds drop the one-way edges into empty / full peers when many nodes are (the
-  // global totals are exact: no prediction), after an all-gather of the class bitmaps
-  // (k <= 8: one keep byte per sender carries the count pass's probes to the emit pass)
-  e->xd_filt = e->xd_planned && e->k <= 8 ? dense_filter(e, est_of(e, e->gtot.data()), e->xd_filter_frac) : 0u;
+  const plan_round p = plan_sharded_round(&e->pl, e->gtot.data());
+  e->sx_planned = p.sparse, e->rep_planned = p.rep, e->xd_planned = p.xd, e->cc_planned = p.cc;
+  e->sx_maj = p.maj;
+  e->sx_alld = p.all_d;
+  e->sx_mid = p.mid;
+  e->xd_filt = p.xd_filt;
   e->xd_cls_ok = false;
-  // dense on the state image: class-coded when few nodes are mixed (neither empty nor full)
-  const double mixed = ((double)e->gtot[4 + e->R] - (double)e->gtot[0]) / (double)e->N;
-  // entering replication over the class-coded all-gather (kind 7): the image expanded whole, then
-  // the replicated round
-  const bool rep_cc = e->rep_planned && !e->rep_img_ok && c.dense_cc;
-  e->cc_planned = (!e->sx_planned && !e->xd_planned && !e->rep_planned && e->cc_frac > 0 && mixed <= e->cc_frac) || rep_cc;
-  *kind = e->sx_planned ? 1 : e->rep_planned ? (e->rep_img_ok ? 6 : rep_cc ? 7 : 5) : e->xd_planned ? 3 : e->cc_planned ? 4 : 0;
+  e->plan_cost[0] = p.sparse_ms;
+  e->plan_cost[1] = p.dense_ms;
+  *kind = p.kind;
   // the model's price of the round as planned (gossip_plan_model): the plan of the current run
   // (restarted at round 0) and the modelled ms since gossip_reset_timing
   if (e->t == 0) e->model_plan.clear();
   e->model_plan.push_back("DSAXCRrQ"[*kind]);
-  e->model_ms += e->sx_planned ? c.sparse : e->rep_planned ? c.rep : c.dense;
-  e->model_link_ms += e->sx_planned ? c.sparse_link : e->rep_planned ? c.rep_link : c.dense_link;
+  e->model_ms += p.ms;
+  e->model_link_ms += p.link_ms;
   e->model_rounds += 1;
   return GOSSIP_OK;
 }
@@ -2709,6 +2519,7 @@ int gossip_set_faults(gossip_engine_t* e, uint32_t edge_loss, uint32_t partition
     return e->fail(GOSSIP_ENOTSUP, "faults: random modes, or a FLOOD engine created with faults or stall_rounds "
                                    "(its per-edge retry state)");
   e->fa = Faults{edge_loss, partitions, e->N, e->stall_d, e->cfg.stall_rounds};
+  e->pl.edge_loss = edge_loss, e->pl.partitions = partitions;
   return GOSSIP_OK;
 }
 

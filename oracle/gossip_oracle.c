@@ -11,6 +11,7 @@
  * OpenMP with atomic ORs for pushes (used only as bench.py's cpu_baseline).
  */
 #include "gossip_oracle.h"
+#include "../gossip-protocol_amd/csrc/plan.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -47,7 +48,7 @@ struct oracle_sim {
   uint64_t* gtot;           /* global totals of S_t [5 + R] */
   int gtot_valid, planned, last_sparse;
   uint32_t maj;
-  double sparse_frac;
+  plan_cfg pl; /* the round planner's shape, knobs (oracle_set_param, oracle_set_faults) and state: csrc/plan.h */
   uint64_t *rare_send, *rare_recv, stride; /* [Nl] items; [G * stride] items */
   uint64_t *msg_send, *msg_recv, msg_cap;  /* [k * nown] items grouped by owner; received items */
   uint64_t* D;                             /* pending push deltas of the owned nodes */
@@ -71,8 +72,7 @@ struct oracle_sim {
   uint64_t nreq, nloc, nin, in_cap, aex_msgs;
   /* exchange dense rounds (kind 3): items {p at owner | flags, S_t[n]} by owner;
    * xnode = the own sender of each send item; replies in send / received order */
-  int xd_planned, sparse_frac_set;
-  uint32_t xd_shards;
+  int xd_planned;
   uint32_t *xid, *xrid;
   uint64_t *xval, *xrval, *xrep_out, *xrep_in, *xnode;
   uint64_t xn_out, xn_in;
@@ -81,17 +81,14 @@ struct oracle_sim {
    * xcls = every shard's [nz][full] occupancy bitmaps of S_t (nwl words each) */
   uint32_t xd_filt;
   int xcls_ok;
-  double xd_filter_frac;
   uint64_t* xcls;
   /* class-coded state all-gather (kind 4): every shard's slot ([nz][full]
    * bitmaps, nwl words each, then nwl uint32 prefixes: the mixed nodes before each bitmap
    * word), the own mixed words, every shard's at q * cc_stride */
   int cc_planned;
-  double cc_frac;
-  /* replicated dense rounds (engine.hip rep_compute, plan kinds 5 / 6): every shard
-   * computes the whole image's round, so the next dense round needs no all-gather */
-  int replicate, rep_planned, rep_img_ok;
-  double link_gbps; /* engine.hip link_gbps: the link-aware plan (0 = the fixed thresholds) */
+  /* replicated dense rounds (plan kinds 5 / 6 / 7): every shard computes the whole
+   * image's round, so the next dense round needs no all-gather (pl.rep_img_ok) */
+  int rep_planned;
   uint64_t *cc_bits, *cc_send, *cc_vals, cc_stride;
 };
 
@@ -255,12 +252,11 @@ int oracle_create(const gossip_config_t* cfg, int threads, oracle_sim_t** out) {
   }
   s->gtot = (uint64_t*)calloc(5 + s->R, 8);
   s->counts = (uint64_t*)calloc(G, 8);
-  s->sparse_frac = 0.25;
-  s->xd_shards = 6;
-  s->cc_frac = 0.75;
-  s->link_gbps = 76.0;
-  s->replicate = -1;
-  s->xd_filter_frac = 0.6; /* engine.hip xd_filter_frac */
+  plan_defaults(&s->pl);
+  s->pl.N = s->N, s->pl.Nl = s->Nl, s->pl.G = G, s->pl.k = s->k, s->pl.R = s->R, s->pl.mode = s->mode;
+  s->pl.edge_loss = cfg->edge_loss, s->pl.partitions = cfg->partitions;
+  /* host shards can run every kind of round (oracle_sharded_plan plans only where sparse_ok) */
+  s->pl.sharded = s->pl.can_sparse = s->pl.can_xd = s->pl.can_rep = 1;
   s->flood_edges = s->mode == GOSSIP_MODE_FLOOD && faulty;
   if (s->flood_edges) {
     const size_t nw = (size_t)s->R * s->N;
@@ -382,7 +378,7 @@ int oracle_reset(oracle_sim_t* s) {
   }
   s->t = 0;
   s->gtot_valid = s->planned = s->last_sparse = 0;
-  s->rep_planned = s->rep_img_ok = 0;
+  s->rep_planned = s->pl.rep_img_ok = 0;
   return GOSSIP_OK;
 }
 
@@ -402,7 +398,7 @@ int oracle_inject(oracle_sim_t* s, uint64_t node, uint32_t rumor) {
     return GOSSIP_OK;
   }
   s->gtot_valid = 0;
-  s->rep_img_ok = 0;
+  s->pl.rep_img_ok = 0;
   if (node < s->lo || node >= s->hi) return GOSSIP_OK;
   uint64_t* w = &s->S[(size_t)(rumor >> 6) * s->Nl + (node - s->lo)];
   if (s->flood_edges && !(*w & (1ull << (rumor & 63)))) { /* a client's value: its walk starts next round */
@@ -852,7 +848,7 @@ int oracle_round_commit(oracle_sim_t* s, const uint64_t* total, gossip_round_sta
     tmp = s->S; s->S = s->Snext; s->Snext = tmp;
   }
   s->last_sparse = 0;
-  s->rep_img_ok = s->rep_planned; /* the image holds S_{t+1} of every node after a replicated round */
+  s->pl.rep_img_ok = s->rep_planned; /* the image holds S_{t+1} of every node after a replicated round */
   s->rep_planned = 0;
   if (s->streak) stall_update(s); /* (uses s->t: the round just computed) */
   memcpy(s->gtot, total, oracle_partial_len(s) * 8);
@@ -871,7 +867,8 @@ int oracle_round_commit(oracle_sim_t* s, const uint64_t* total, gossip_round_sta
 
 /* ---------------- sparse sharded rounds (include/gossip.h) --------
  * Plain restatement of the engine's protocol for the driver tests: the same
- * plan rule, items and phases; lookups by binary search in the sorted lists. */
+ * items and phases, planned by the same csrc/plan.h (the plan changes no result);
+ * lookups by binary search in the sorted lists. */
 
 static int sparse_ok(const oracle_sim_t* s) {
   return s->G > 1 && s->W == 1 && s->mode >= GOSSIP_MODE_PUSH && s->mode <= GOSSIP_MODE_PUSHPULL;
@@ -905,77 +902,6 @@ int oracle_local_totals(oracle_sim_t* s, uint64_t* partial) {
   return GOSSIP_OK;
 }
 
-/* The engine's per-rank cost model of one sharded round (engine.hip shard_round_costs), in ms, at
- * nz nonzero and full_n full nodes: the sparse round, the dense round of the kind the plan would
- * pick (exchange / class-coded / state all-gather), the replicated round's device time and the
- * state all-gather that enters it. */
-static void plan_costs(const oracle_sim_t* s, double nz, double full_n, double* c_sparse, double* c_dense,
-                       double* c_rep, double* c_gather) {
-  const double N = (double)s->N, G = (double)s->G, Nl = (double)s->Nl, k = (double)s->k;
-  const double rare = nz < N - full_n ? nz : N - full_n, rare_own = rare / G;
-  const double bw = s->link_gbps * 1e6 * (G - 1.0 < 7.0 ? G - 1.0 : 7.0);
-  *c_sparse = Nl * (2.3e-9 + 7.0e-8 * (1.0 - exp(-rare / N / 0.05))) +
-              (16.0 * rare_own * (G - 1.0) + 16.0 * k * rare_own * (G - 1.0) / G) / bw;
-  const int dense_xd = s->xd_shards && s->G >= s->xd_shards;
-  const double mixed_n = nz - full_n > 0.0 ? nz - full_n : 0.0;
-  const int dense_cc = !dense_xd && s->cc_frac > 0 && mixed_n / N <= s->cc_frac;
-  if (dense_xd) { /* the items that survive the class filter (the engine's dense_filter) */
-    unsigned filt = 0;
-    if (s->k <= 8) {
-      const double empty = 1.0 - nz / N, full = full_n / N;
-      const int can_pull = s->mode != GOSSIP_MODE_PUSH, can_push = s->mode != GOSSIP_MODE_PULL;
-      filt = (can_pull && empty > s->xd_filter_frac ? 1u : 0u) | (can_push && full > s->xd_filter_frac ? 2u : 0u);
-    }
-    const double ef = 1.0 - nz / N, ff = full_n / N;
-    const double mf = 1.0 - ef - ff > 0.0 ? 1.0 - ef - ff : 0.0;
-    const double kept = mf + ef * ((filt & 1u) ? 1.0 - ef : 1.0) + ff * ((filt & 2u) ? 1.0 - ff : 1.0);
-    *c_dense = Nl * (4.85e-8 + 2.0e-8 * kept) + 40.0 * (G - 1.0) / G * Nl * kept / bw;
-  } else {
-    const double slice = dense_cc ? 20.0 / 64.0 * Nl + 8.0 * mixed_n / G : 8.0 * Nl;
-    *c_dense = 7.3e-9 * N + 4.7e-8 * Nl + slice * (G - 1.0) / bw;
-  }
-  *c_rep = 3.8e-8 * N + 1.5e-9 * Nl;
-  /* entering replication gathers the image class-coded where the dense round would (kind 7) */
-  *c_gather = (dense_cc ? 20.0 / 64.0 * Nl + 8.0 * mixed_n / G : 8.0 * Nl) * (G - 1.0) / bw;
-}
-
-/* The engine's mean-field predictor (engine.hip predict): one round of every rumor's holder count
- * inf[r]; returns the predicted nonzero and full node counts. */
-static void predict_round(const oracle_sim_t* s, double* inf, double* nz, double* full) {
-  const double keep = (1.0 - (double)s->cfg.edge_loss / 4294967296.0) *
-                      (s->cfg.partitions > 1 ? 1.0 / s->cfg.partitions : 1.0);
-  const double N = (double)s->N, k = (double)s->k * keep;
-  const int push = s->mode == GOSSIP_MODE_PUSH || s->mode == GOSSIP_MODE_PUSHPULL;
-  const int pull = s->mode == GOSSIP_MODE_PULL || s->mode == GOSSIP_MODE_PUSHPULL;
-  double all_miss = 1.0, all_hit = 1.0;
-  for (uint32_t r = 0; r < s->R; ++r) {
-    const double u = 1.0 - inf[r] / N;
-    double v = u;
-    if (pull) v *= pow(u, k);
-    if (push) v *= exp(-k * (1.0 - u));
-    inf[r] = (1.0 - v) * N;
-    all_miss *= v;
-    all_hit *= 1.0 - v;
-  }
-  *nz = N * (1.0 - all_miss);
-  *full = N * all_hit;
-}
-
-/* The engine's rep_gain_ahead: what replicating saves over the dense rounds after this one, up to
- * 8 predicted rounds, until one the model would run sparse. */
-static double rep_gain_ahead(const oracle_sim_t* s) {
-  double inf[64], nz = 0, full = 0, gain = 0.0;
-  for (uint32_t r = 0; r < s->R && r < 64; ++r) inf[r] = (double)s->gtot[4 + r];
-  for (int i = 0; i < 8; ++i) {
-    predict_round(s, inf, &nz, &full);
-    double c_sparse, c_dense, c_rep, c_gather;
-    plan_costs(s, nz, full, &c_sparse, &c_dense, &c_rep, &c_gather);
-    if (c_sparse < (c_dense < c_rep ? c_dense : c_rep)) break;
-    gain += c_dense - c_rep > 0.0 ? c_dense - c_rep : 0.0;
-  }
-  return gain;
-}
-
 int oracle_sharded_plan(oracle_sim_t* s, const uint64_t* total, int32_t* kind) {
   if (!s || !kind) return GOSSIP_EINVAL;
   s->planned = s->xd_planned = s->cc_planned = s->rep_planned = 0;
@@ -995,44 +921,12 @@ int oracle_sharded_plan(oracle_sim_t* s, const uint64_t* total, int32_t* kind) {
     *kind = -1;
     return GOSSIP_OK;
   }
-  const double nz = (double)s->gtot[4 + s->R], notfull = (double)s->N - (double)s->gtot[0];
-  s->maj = notfull < nz;
-  /* the engine's default threshold (engine.hip sparse_frac_of): 1/25 before exchange rounds */
-  const double frac = s->sparse_frac_set ? s->sparse_frac : s->xd_shards && s->G >= s->xd_shards ? 0.04 : 0.25;
-  s->planned = (notfull < nz ? notfull : nz) <= frac * (double)s->N;
-  /* the engine's replicated round (shard_round_costs' rep): the one-GPU round over all N nodes,
-   * plus the state all-gather while the image is not whole */
-  if (!s->sparse_frac_set && s->link_gbps > 0) { /* the engine's link-aware cost model (shard_round_costs) */
-    const double full_n = (double)s->gtot[0];
-    double c_sparse, c_dense, c_rep, c_gather;
-    plan_costs(s, nz, full_n, &c_sparse, &c_dense, &c_rep, &c_gather);
-    const double c_rep_all = c_rep + (s->rep_img_ok ? 0.0 : c_gather);
-    /* the engine's rep_auto: with a whole image while cheaper than the sharded dense round; entering
-     * where the extra cost is won back over the dense rounds the mean-field predictor sees ahead */
-    int rep_auto = s->replicate < 0 && s->N >= (1ull << 22) && c_rep < c_dense;
-    if (rep_auto && !s->rep_img_ok) rep_auto = c_rep_all - c_dense < rep_gain_ahead(s);
-    s->planned = c_sparse < ((s->replicate == 1 || rep_auto) && c_rep_all < c_dense ? c_rep_all : c_dense);
-    s->rep_planned = !s->planned && rep_auto;
-  }
-  /* (the engine's rep_any: forced, or the model's choice above, past 2^22 nodes) */
-  if (s->replicate == 1) s->rep_planned = !s->planned;
-  s->xd_planned = !s->planned && !s->rep_planned && s->xd_shards && s->G >= s->xd_shards;
-  /* the engine's dense_filter of the global totals (engine.hip): pulls from empty peers once more
-   * than xd_filter_frac of the nodes are empty, pushes into full peers likewise */
-  s->xd_filt = 0;
+  const plan_round p = plan_sharded_round(&s->pl, s->gtot);
+  s->planned = p.sparse, s->rep_planned = p.rep, s->xd_planned = p.xd, s->cc_planned = p.cc;
+  s->maj = p.maj;
+  s->xd_filt = p.xd_filt;
   s->xcls_ok = 0;
-  if (s->xd_planned && s->k <= 8) { /* the engine keeps one verdict byte per sender: k <= 8 */
-    const double empty = 1.0 - nz / (double)s->N, full = (double)s->gtot[0] / (double)s->N;
-    const int can_pull = s->mode != GOSSIP_MODE_PUSH, can_push = s->mode != GOSSIP_MODE_PULL;
-    s->xd_filt = (can_pull && empty > s->xd_filter_frac ? 1u : 0u) | (can_push && full > s->xd_filter_frac ? 2u : 0u);
-  }
-  /* the engine's class-coded all-gather: at most cc_frac mixed (nonzero, not full) nodes */
-  const double mixed = ((double)s->gtot[4 + s->R] - (double)s->gtot[0]) / (double)s->N;
-  /* the engine's kind 7: entering replication over the class-coded all-gather */
-  const int rep_cc = s->rep_planned && !s->rep_img_ok && !(s->xd_shards && s->G >= s->xd_shards) &&
-                     s->cc_frac > 0 && mixed <= s->cc_frac;
-  s->cc_planned = (!s->planned && !s->xd_planned && !s->rep_planned && s->cc_frac > 0 && mixed <= s->cc_frac) || rep_cc;
-  *kind = s->planned ? 1 : s->rep_planned ? (s->rep_img_ok ? 6 : rep_cc ? 7 : 5) : s->xd_planned ? 3 : s->cc_planned ? 4 : 0;
+  *kind = p.kind;
   return GOSSIP_OK;
 }
 
@@ -1385,38 +1279,38 @@ int oracle_cc_expand(oracle_sim_t* s, const uint64_t* counts) {
 }
 
 /* gossip_set_param: the engine's tuning knobs.  sparse_frac, link_gbps, cc_frac, xd_shards,
- * xd_filter_frac and replicate matter here (they pick the
- * sharded round protocol, which the gloo tests exercise); the rest steer engine kernel
+ * xd_filter_frac and replicate matter here (plan.h picks the sharded round
+ * protocol from them, which the gloo tests exercise); the rest steer engine kernel
  * choices that this restatement does not have, and are accepted as no-ops. */
 int oracle_set_param(oracle_sim_t* s, const char* name, double value) {
   if (!s || !name) return GOSSIP_EINVAL;
   if (!strcmp(name, "sparse_frac")) {
-    s->sparse_frac = value;
-    s->sparse_frac_set = 1;
+    s->pl.sparse_frac = value;
+    s->pl.sparse_frac_set = 1;
     return GOSSIP_OK;
   }
   if (!strcmp(name, "link_gbps")) {
     if (value < 0) return GOSSIP_EINVAL;
-    s->link_gbps = value;
+    s->pl.link_gbps = value;
     return GOSSIP_OK;
   }
   if (!strcmp(name, "replicate")) { /* < 0: by the cost model, 0: never, > 0: every dense round */
-    s->replicate = value < 0 ? -1 : value > 0 ? 1 : 0;
+    s->pl.replicate = value < 0 ? -1 : value > 0 ? 1 : 0;
     return GOSSIP_OK;
   }
   if (!strcmp(name, "cc_frac")) {
     if (value < 0 || value > 1) return GOSSIP_EINVAL;
-    s->cc_frac = value;
+    s->pl.cc_frac = value;
     return GOSSIP_OK;
   }
   if (!strcmp(name, "xd_shards")) {
     if (value < 0 || value > 1024) return GOSSIP_EINVAL;
-    s->xd_shards = (uint32_t)value;
+    s->pl.xd_shards = (uint32_t)value;
     return GOSSIP_OK;
   }
   if (!strcmp(name, "xd_filter_frac")) {
     if (value < 0 || value > 1) return GOSSIP_EINVAL;
-    s->xd_filter_frac = value;
+    s->pl.xd_filter_frac = value;
     return GOSSIP_OK;
   }
   /* the engine's performance knobs (path choice, grids): no effect on the rounds' results */
@@ -1435,6 +1329,7 @@ int oracle_set_faults(oracle_sim_t* s, uint32_t edge_loss, uint32_t partitions) 
     return GOSSIP_ENOTSUP; /* FLOOD retries need the per-edge state: create with faults or stall_rounds */
   s->cfg.edge_loss = edge_loss;
   s->cfg.partitions = partitions;
+  s->pl.edge_loss = edge_loss, s->pl.partitions = partitions;
   return GOSSIP_OK;
 }
 

@@ -367,7 +367,7 @@ def dense_filter(S, N, R, mode, k, frac):
 
 
 def rare_is_not_full(S, N, R):
-    """choose_sparse: the rare class is not-full iff N - full < nonzero, else nonzero"""
+    """plan_choose_sparse: the rare class is not-full iff N - full < nonzero, else nonzero"""
     return N - int((S == full_mask(R)).sum()) < int((S != 0).sum())
 
 

@@ -171,7 +171,7 @@ def _timed_run(work, mode, k, name, path, loss=0, parts=0):
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "-".join(str(x) for x in c))
 def test_built_states_every_path(case, path):
     """Empty and full nodes side by side, full-majority rounds with the rare nodes on group and
-    tile boundaries (`holes`), perfectly correlated rumors (`clustered`).  By dense_filter() a
+    tile boundaries (`holes`), perfectly correlated rumors (`clustered`).  By plan_dense_filter() a
     round that starts with both shares above 0.3 sets the push-into-full bit in push and push-pull
     mode and the pull-from-empty bit in pull and push-pull mode, so emit runs with both bits
     (filter 3) in `thirds` push-pull round 0 and `clustered` push-pull k=1 round 4 — on
@@ -202,7 +202,7 @@ PREDICT = {"clustered": ("push", 1), "disjoint": ("pushpull", 2), "philox100k": 
 @pytest.mark.parametrize("path", ["auto", "sparse", "sparse_direct", "sparse_bscan", "dense_filter"])
 @pytest.mark.parametrize("work", list(PREDICT))
 def test_wrong_prediction_only_costs_time(work, path, ahead):
-    """predict() multiplies per-rumor miss probabilities as if rumors were independent: with
+    """plan_predict() multiplies per-rumor miss probabilities as if rumors were independent: with
     perfectly correlated rumors (`clustered`) it sees far too many nonzero nodes a round ahead,
     with disjoint ones too few, so with 7 rounds in flight maj, all_d, the filter bits and the
     binned-scan choice are picked for a state that is not there.  One step(64), then the same run

@@ -31,7 +31,7 @@ ROUNDS = {
     ("disjoint", "pushpull", 2, 0, 0): 5,
 }
 
-# rounds that start with more than 0.3 of the nodes empty and more than 0.3 full (dense_filter()'s
+# rounds that start with more than 0.3 of the nodes empty and more than 0.3 full (plan_dense_filter()'s
 # default threshold): (empty, full) shares to 3 places at the start of the round
 BOTH_CLASSES = {
     ("thirds", "pushpull", 2, 0, 0): {0: (0.333, 0.333)},

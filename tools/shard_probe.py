@@ -89,7 +89,7 @@ for rep in range(2):
                   flush=True)
         print(f"G={G} rounds={len(rounds)} sum per-rank {sum(r[2] for r in rounds):.2f} ms  "
               f"gathered per rank {sum(r[5] for r in rounds) / 2**20:.1f} MiB", flush=True)
-        # the planner's link term (engine.hip shard_round_costs): the bytes a rank receives (= what it
+        # the planner's link term (csrc/plan.h plan_round_costs): the bytes a rank receives (= what it
         # sends, by symmetry) over link_gbps x min(G - 1, 7) links, added to the device time
         bw = PARAMS.get("link_gbps", 76.0) or 76.0
         link_ms = sum(r[5] for r in rounds) / (bw * 1e6 * min(G - 1, 7))
