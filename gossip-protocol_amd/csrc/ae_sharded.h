@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "philox.h"
+
 namespace gossip {
 
 struct AexArgs {
@@ -27,6 +29,7 @@ struct AexArgs {
   uint8_t* verdict;         // [nown] per own node, from the count pass: bit j = exchange j listed (k <= 8)
   uint64_t N, Nl, lo, nown;
   uint32_t G, rank, K, L, k, t, key0, key1, fail, rec, flags, rw, pw;
+  Faults fa;                // lost edges (global N, stall null): the same on every rank
 };
 
 // entries of the per-block tables (bcnt, boff) for nown own nodes and G shards

@@ -64,7 +64,10 @@ __device__ __forceinline__ void block_range(const AexArgs& a, uint64_t* i0, uint
 // FILL = false: per-block item counts per owner (+ own-own exchanges in slot G) into
 // bcnt[b][G + 1] and the messages into partial[2].  FILL = true: the same walk, items
 // written at boff[b][q] + LDS cursor (request items {p, n, row[K]}, own-own pairs).
-template <bool FILL>
+// FAULTS: a lost edge (philox.h edge_lost) is no message and lists nothing.  The
+// count pass decides; the k <= 8 fill pass follows its verdicts, the k > 8 one redraws the loss
+// words and applies the same test, so both passes count the same items per owner.
+template <bool FILL, bool FAULTS>
 __global__ __launch_bounds__(kAxBlock) void aex_list_kernel(AexArgs a, uint32_t* bcnt, const uint64_t* boff) {
   constexpr uint32_t kStage = kAxBlock * 8;  // items one pass of the block lists at most (k <= 8)
   __shared__ uint32_t c[kAxMaxG + 1];
@@ -100,16 +103,21 @@ __global__ __launch_bounds__(kAxBlock) void aex_list_kernel(AexArgs a, uint32_t*
       sn = go && stale_in(wn, n);
     }
     if (go) {
-      u32x4 x{0, 0, 0, 0};
+      u32x4 x{0, 0, 0, 0}, lw{0, 0, 0, 0};
       uint32_t listed = 0;
+      const bool decide = !(FILL && verdicts);  // this pass tests the edges itself
+      Reach rc{0u, 0xFFFFFFFFu};
+      if (FAULTS && decide) rc = reach_of((uint32_t)n, a.fa);
       for (uint32_t j = 0; j < a.k; ++j) {
         if ((j & 3u) == 0) x = philox4x32_10(u32x4{(uint32_t)n, a.t, 0u, j >> 2}, a.key0, a.key1);
         const uint32_t p = peer_from_word(lane_of(x, j & 3u), nm1, (uint32_t)n);
+        if (FAULTS && decide && (j & 3u) == 0 && a.fa.loss) lw = loss_draws((uint32_t)n, a.t, j >> 2, a.key0, a.key1);
         if (FILL && verdicts) {
           if (!((vb >> j) & 1u)) continue;
         } else {
           const uint4 wp = pair_of(a.img, p);
           if (!alive_in(wp, p)) continue;
+          if (FAULTS && edge_lost(a.fa, rc, p, lane_of(lw, j & 3u))) continue;  // (no loss rate: lw = 0)
           ++msgs;
           if (!sn && !stale_in(wp, p)) continue;  // two target rows: nothing moves
           listed |= 1u << j;
@@ -518,10 +526,13 @@ hipError_t launch_aex_requests(const AexArgs& a, hipStream_t st) {
   const uint32_t nb = list_blocks(a.nown);
   uint32_t* bcnt = a.bcnt;
   uint64_t* boff = a.boff;
-  aex_list_kernel<false><<<nb, kAxBlock, 0, st>>>(a, bcnt, nullptr);
+  const bool faults = a.fa.any();
+  if (faults) aex_list_kernel<false, true><<<nb, kAxBlock, 0, st>>>(a, bcnt, nullptr);
+  else aex_list_kernel<false, false><<<nb, kAxBlock, 0, st>>>(a, bcnt, nullptr);
   aex_total_kernel<<<a.G + 1, kAxBlock, 0, st>>>(a, bcnt, nb);
   aex_scan_kernel<<<a.G + 1, kAxBlock, 0, st>>>(a, bcnt, boff, nb);
-  aex_list_kernel<true><<<nb, kAxBlock, 0, st>>>(a, bcnt, boff);
+  if (faults) aex_list_kernel<true, true><<<nb, kAxBlock, 0, st>>>(a, bcnt, boff);
+  else aex_list_kernel<true, false><<<nb, kAxBlock, 0, st>>>(a, bcnt, boff);
   return hipGetLastError();
 }
 

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "philox.h"
+
 namespace gossip {
 
 // AeArgs::flags bit (internal, above the ABI's GOSSIP_FLAG_*): the stale bits of S_t in ab are
@@ -57,6 +59,16 @@ struct AeArgs {
   uint32_t pl, nzero;
 };
 
+// A round's arguments with its lost edges: an exchange n -> p_j whose edge is lost
+// (philox.h edge_lost: a partition between its ends, or its loss draw) does not take place, in
+// either direction.  stall stays null (ANTIENTROPY has no stall model).  This is what the engine
+// builds (make_ae_args) and every round launch takes.  fa.any() picks the kernels' FAULTS
+// instantiations, which receive the whole struct; the others receive the AeArgs part alone, so an
+// engine without faults runs kernels with no fault code and the argument layout they always had.
+struct AeFArgs : AeArgs {
+  Faults fa;
+};
+
 // binned sparse-scan geometry for N nodes, k exchanges per node
 struct AeBinGeom {
   uint32_t tl, nt, rs, nreg;
@@ -72,15 +84,15 @@ hipError_t launch_ae_fill_alive(uint64_t* ab, uint64_t N, hipStream_t st);
 // churn of round t: ab -> abn (alive bits churned, stale bits carried)
 hipError_t launch_ae_churn(const AeArgs& a, hipStream_t st);
 // dense round (after the churn): pull pass writes every row of Vn, push pass atomicMax into Vn
-hipError_t launch_ae_round(const AeArgs& a, hipStream_t st);
+hipError_t launch_ae_round(const AeFArgs& a, hipStream_t st);
 // stats of (V, the alive bits of ab); write_stale also rebuilds ab's stale bits and aux[0]
 hipError_t launch_ae_stats(const AeArgs& a, const uint32_t* V, uint64_t* ab, bool write_stale, hipStream_t st);
 // sparse round (after the churn): scan (edges touching a stale node), gather, apply in
 // place, fix-up (stale bits, hash delta into partial[3]), then stats from the bitmaps
-hipError_t launch_ae_sparse(const AeArgs& a, hipStream_t st);
+hipError_t launch_ae_sparse(const AeFArgs& a, hipStream_t st);
 // the same round with the binned scan (a.brec set, a.nseg == a.bnt); its first
 // pass also does the churn (no launch_ae_churn before it)
-hipError_t launch_ae_sparse_binned(const AeArgs& a, hipStream_t st);
+hipError_t launch_ae_sparse_binned(const AeFArgs& a, hipStream_t st);
 hipError_t launch_ae_sparse_stats(const AeArgs& a, hipStream_t st);
 // binned dense round: geometry of its 2^14-node tiles (the sparse scan's
 // sender regions), whether the kernels' LDS tables cover it, and the round itself: the
@@ -90,6 +102,6 @@ hipError_t launch_ae_sparse_stats(const AeArgs& a, hipStream_t st);
 // overflowed the LDS list, rerun the round with launch_ae_round
 AeBinGeom ae_dense_geom(uint64_t N, uint32_t k);
 bool ae_dense_fits(const AeBinGeom& g, uint64_t N, uint32_t k, uint32_t K);
-hipError_t launch_ae_dense_binned(const AeArgs& a, hipStream_t st);
+hipError_t launch_ae_dense_binned(const AeFArgs& a, hipStream_t st);
 
 }  // namespace gossip

@@ -5,7 +5,9 @@
 // then every alive node n exchanges with its Philox peers p_j(n,t) that are
 // alive too: both take the elementwise max of the two S_t rows.  The
 // reference's only failure handling is retry-until-acked (main.go:77-87);
-// churn here is the build-defined fault model of SURVEY.md §5.
+// churn here is the build-defined fault model of SURVEY.md §5.  Edge loss and
+// partitions drop single exchanges on top of it: AeEdges below,
+// in the FAULTS instantiations of the kernels that decide an exchange from a draw.
 //
 // Every kernel walks 64-node chunks, one chunk per wave.  The node phase runs
 // one lane per node (Philox peer draw, the peer's alive bit from the churn
@@ -134,6 +136,30 @@ __device__ __forceinline__ uint32_t peer_j(const AeArgs& a, uint32_t n, uint32_t
   return peer_from_word(lane_of(x, j & 3u), a.N - 1, n);
 }
 
+// The lost edges of node n's exchanges in round a.t (philox.h edge_lost): n's
+// partition block once per node, the loss words once per Philox block and only with a loss rate.
+// lost(j, p) is asked for j = 0, 1, ... in order (every j, as peer_j), so every kernel that decides
+// an exchange from a peer draw makes the same decision.  FAULTS = false: no code at all.
+// A FAULTS kernel takes the round's arguments with the faults (AeFArgs), the others AeArgs alone.
+template <bool FAULTS>
+using AeK = typename std::conditional<FAULTS, AeFArgs, AeArgs>::type;
+
+template <bool FAULTS>
+struct AeEdges {
+  Reach rc;
+  u32x4 lw;
+  __device__ __forceinline__ AeEdges(const AeFArgs& a, uint32_t n) : rc(reach_of(n, a.fa)), lw{0u, 0u, 0u, 0u} {}
+  __device__ __forceinline__ bool lost(const AeFArgs& a, uint32_t n, uint32_t j, uint32_t p) {
+    if ((j & 3u) == 0 && a.fa.loss) lw = loss_draws(n, a.t, j >> 2, a.key0, a.key1);
+    return edge_lost(a.fa, rc, p, lane_of(lw, j & 3u));  // (no loss rate: lw = 0 is never below it)
+  }
+};
+template <>
+struct AeEdges<false> {  // no faults: no state, no code
+  __device__ __forceinline__ AeEdges(const AeArgs&, uint32_t) {}
+  __device__ __forceinline__ bool lost(const AeArgs&, uint32_t, uint32_t, uint32_t) { return false; }
+};
+
 __global__ __launch_bounds__(kAeBlock) void ae_fill_alive_kernel(uint64_t* ab, uint64_t N) {
   const uint64_t nw = (N + 63) / 64;
   for (uint64_t w = (uint64_t)blockIdx.x * kAeBlock + threadIdx.x; w < nw; w += (uint64_t)gridDim.x * kAeBlock) {
@@ -175,8 +201,8 @@ struct MaskOf {  // one bit per lane of a node's group
 // pull pass: Vn[n] = max(V[n], V[p_j] for every exchange j of n) — plain stores of
 // every row — and, per exchange, the mask of components where V[n] > V[p_j]: the
 // push pass then needs neither the peer's row nor its alive bit
-template <uint32_t L>
-__global__ __launch_bounds__(kAeBlock) void ae_pull_kernel(AeArgs a) {
+template <uint32_t L, bool FAULTS>
+__global__ __launch_bounds__(kAeBlock) void ae_pull_kernel(AeK<FAULTS> a) {
   using MT = typename MaskOf<L>::T;
   constexpr uint32_t per = 64 / L;
   constexpr uint64_t gmask = L >= 64 ? ~0ull : ((1ull << L) - 1ull);
@@ -198,12 +224,14 @@ __global__ __launch_bounds__(kAeBlock) void ae_pull_kernel(AeArgs a) {
       acc[i] = own[i];
     }
     u32x4 x{0, 0, 0, 0};
+    AeEdges<FAULTS> fe(a, n);
     for (uint32_t j = 0; j < a.k; ++j) {
       uint32_t p = 0;
       bool ex = false;
       if (aln) {
         p = peer_j(a, n, j, x);
-        ex = alive_bit(a.abn, p);
+        const bool lost = fe.lost(a, n, j, p);  // (every j: the loss words are drawn at j % 4 == 0)
+        ex = alive_bit(a.abn, p) && !lost;
       }
       msgs += ex ? 1u : 0u;
       if (!__ballot(ex)) {
@@ -348,7 +376,8 @@ __global__ __launch_bounds__(kAeBlock) void ae_stats_kernel(AeArgs a, const uint
 // --------------------------------------------------------------- sparse round
 // Scan: block b owns chunks [b*spc, (b+1)*spc) and lists, into its own segment,
 // the exchanges with a stale end (LDS slot counter); past segcap only counted.
-__global__ __launch_bounds__(kAeBlock) void ae_sparse_scan_kernel(AeArgs a) {
+template <bool FAULTS>
+__global__ __launch_bounds__(kAeBlock) void ae_sparse_scan_kernel(AeK<FAULTS> a) {
   __shared__ uint64_t red[kAeWaves];
   __shared__ uint32_t scnt;
   const uint32_t lane = threadIdx.x & 63;
@@ -365,12 +394,14 @@ __global__ __launch_bounds__(kAeBlock) void ae_sparse_scan_kernel(AeArgs a) {
     const bool aln = (a.abn[2 * ch] >> lane) & 1ull;
     const bool own_stale = (a.abn[2 * ch + 1] >> lane) & 1ull;
     u32x4 x{0, 0, 0, 0};
+    AeEdges<FAULTS> fe(a, n);
     for (uint32_t j = 0; j < a.k; ++j) {
       uint32_t p = 0;
       bool ex = false, pst = false;
       if (aln) {
         p = peer_j(a, n, j, x);
         alive_stale(a.abn, p, &ex, &pst);
+        if (fe.lost(a, n, j, p)) ex = false;
       }
       msgs += ex ? 1u : 0u;
       const bool need = ex && (own_stale || pst);
@@ -417,8 +448,12 @@ constexpr int kAeEmitWaves = 8;  // waves per SIMD: 8 = two blocks per CU (<= 64
 // 0.568 ms per sparse round redrawing them, profiles/r02_ae_one)
 // NT: LDS tile counters (kAeBinTiles for the sparse scan's tiles, two blocks per CU;
 // kAeDTiles for the dense round's 2^14-node tiles, one block per CU)
-template <bool K1, uint32_t NT>
-__global__ __launch_bounds__(kAeBinThreads, (NT > kAeBinTiles ? 4 : kAeEmitWaves)) void ae_bin_emit_kernel(AeArgs a) {
+// FAULTS: a lost edge produces no record.  Pass A and pass B drop the same edges:
+// k == 1 keeps the verdict with the peer (kAeNoPeer, no node id: p <= N - 1 < 2^32 - 1), the
+// other form redraws the loss words in pass B through the same AeEdges as pass A.
+constexpr uint32_t kAeNoPeer = 0xFFFFFFFFu;
+template <bool K1, uint32_t NT, bool FAULTS>
+__global__ __launch_bounds__(kAeBinThreads, (NT > kAeBinTiles ? 4 : kAeEmitWaves)) void ae_bin_emit_kernel(AeK<FAULTS> a) {
   __shared__ uint32_t cur[NT];
   __shared__ __align__(16) uint32_t st[kAeBinRec];  // read back as uint4
   __shared__ uint32_t wsum[kAeBinThreads / 64];
@@ -466,12 +501,14 @@ __global__ __launch_bounds__(kAeBinThreads, (NT > kAeBinTiles ? 4 : kAeEmitWaves
       if (!al) continue;
       live |= 1u << q;
       stl |= (uint32_t)((sw >> lane) & 1ull) << q;
+      AeEdges<FAULTS> fe(a, (uint32_t)n);
       for (uint32_t j = 0; j < a.k; ++j) {
         // (x already holds the draw of j < 4 when k <= 3)
         const uint32_t p =
             j == 0 && a.k <= 3 ? peer_from_word(x.x, a.N - 1, (uint32_t)n) : peer_j(a, (uint32_t)n, j, x);
-        if (K1) pr[q] = p;
-        atomicAdd(&cur[p >> a.btl], 1u);
+        const bool lost = fe.lost(a, (uint32_t)n, j, p);
+        if (K1) pr[q] = lost ? kAeNoPeer : p;
+        if (!lost) atomicAdd(&cur[p >> a.btl], 1u);
       }
     }
     __syncthreads();
@@ -516,11 +553,14 @@ __global__ __launch_bounds__(kAeBinThreads, (NT > kAeBinTiles ? 4 : kAeEmitWaves
       const uint32_t nl = q * kAeBinThreads + tid, sb = (stl >> q) & 1u;
       if (K1) {
         const uint32_t p = pr[q];
-        st[atomicAdd(&cur[p >> a.btl], 1u)] = ae_rec(p & tmask, nl, sb, a.btl, a.brs);
+        if (!FAULTS || p != kAeNoPeer)
+          st[atomicAdd(&cur[p >> a.btl], 1u)] = ae_rec(p & tmask, nl, sb, a.btl, a.brs);
       } else {
         u32x4 x{0, 0, 0, 0};
+        AeEdges<FAULTS> fe(a, (uint32_t)n);
         for (uint32_t j = 0; j < a.k; ++j) {
           const uint32_t p = peer_j(a, (uint32_t)n, j, x);
+          if (fe.lost(a, (uint32_t)n, j, p)) continue;
           st[atomicAdd(&cur[p >> a.btl], 1u)] = ae_rec(p & tmask, nl, sb, a.btl, a.brs);
         }
       }
@@ -818,8 +858,9 @@ __device__ __forceinline__ uint32_t ae_tile_of(uint32_t nt) {
   return (nt & 7u) ? blockIdx.x : (blockIdx.x & 7u) * (nt >> 3) + (blockIdx.x >> 3);
 }
 
-template <uint32_t L, uint32_t KJ>  // KJ = k (<= 3)
-__global__ __launch_bounds__(kAeDThreads) void ae_dense_apply_kernel(AeArgs a) {
+// FAULTS: the pull side folds the emit's edge test into exj, so it agrees with the records dropped
+template <uint32_t L, uint32_t KJ, bool FAULTS>  // KJ = k (<= 3)
+__global__ __launch_bounds__(kAeDThreads) void ae_dense_apply_kernel(AeK<FAULTS> a) {
   static_assert(L <= 16, "per-wave LDS scratch of 64 x L words");
   constexpr uint32_t per = 64 / L;
   constexpr uint64_t gmask = L >= 64 ? ~0ull : ((1ull << L) - 1ull);
@@ -887,6 +928,10 @@ __global__ __launch_bounds__(kAeDThreads) void ae_dense_apply_kernel(AeArgs a) {
       u32x4 x{0, 0, 0, 0};
 #pragma unroll
       for (uint32_t j = 0; j < KJ; ++j) pj[j] = aln ? peer_j(a, n, j, x) : 0u;
+      bool lj[KJ];  // the edge n -> pj[j] is lost (one Philox block: KJ <= 3)
+      AeEdges<FAULTS> fe(a, n);
+#pragma unroll
+      for (uint32_t j = 0; j < KJ; ++j) lj[j] = aln && fe.lost(a, n, j, pj[j]);
       uint32_t vp[KJ][L];
 #pragma unroll
       for (uint32_t j = 0; j < KJ; ++j) {
@@ -899,7 +944,7 @@ __global__ __launch_bounds__(kAeDThreads) void ae_dense_apply_kernel(AeArgs a) {
         }
       }
 #pragma unroll
-      for (uint32_t j = 0; j < KJ; ++j) exj[j] = aln && alive_bit(a.abn, pj[j]);
+      for (uint32_t j = 0; j < KJ; ++j) exj[j] = aln && alive_bit(a.abn, pj[j]) && !lj[j];
       auto in_group = [&](uint32_t f0) {
         uint32_t vi[kB], ti[kB];
 #pragma unroll
@@ -973,8 +1018,8 @@ __device__ __forceinline__ uint4 max4(uint4 x, uint4 y) {
   return uint4{max(x.x, y.x), max(x.y, y.y), max(x.z, y.z), max(x.w, y.w)};
 }
 
-template <uint32_t KJ>
-__global__ __launch_bounds__(kAeQThreads) void ae_dense_apply_q_kernel(AeArgs a) {
+template <uint32_t KJ, bool FAULTS>
+__global__ __launch_bounds__(kAeQThreads) void ae_dense_apply_q_kernel(AeK<FAULTS> a) {
   constexpr uint32_t kW = kAeQThreads / 64;
   constexpr uint32_t kBQ = 4;  // in-edge piece groups in flight (16 edges each)
   __shared__ uint32_t pos2[kAeDTile / 2];
@@ -1033,6 +1078,10 @@ __global__ __launch_bounds__(kAeQThreads) void ae_dense_apply_q_kernel(AeArgs a)
       u32x4 x{0, 0, 0, 0};
 #pragma unroll
       for (uint32_t j = 0; j < KJ; ++j) pj[j] = aln ? peer_j(a, n, j, x) : 0u;
+      bool lj[KJ];  // the edge n -> pj[j] is lost (one Philox block: KJ <= 3)
+      AeEdges<FAULTS> fe(a, n);
+#pragma unroll
+      for (uint32_t j = 0; j < KJ; ++j) lj[j] = aln && fe.lost(a, n, j, pj[j]);
       // every peer row is gathered at once; the alive bits are checked after (awaiting them
       // first costs a round trip per chunk: DESIGN.md §3.8)
       uint4 vp[KJ][4];
@@ -1046,7 +1095,7 @@ __global__ __launch_bounds__(kAeQThreads) void ae_dense_apply_q_kernel(AeArgs a)
           vp[j][g] = go ? *row(pp) : uint4{0, 0, 0, 0};
         }
 #pragma unroll
-      for (uint32_t j = 0; j < KJ; ++j) exj[j] = aln && alive_bit(a.abn, pj[j]);
+      for (uint32_t j = 0; j < KJ; ++j) exj[j] = aln && alive_bit(a.abn, pj[j]) && !lj[j];
       auto in_group = [&](uint32_t f0) {
         uint4 vi[kBQ];
         uint32_t ti[kBQ];
@@ -1312,8 +1361,61 @@ hipError_t launch_ae_churn(const AeArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_ae_round(const AeArgs& a, hipStream_t st) {
-  AE_LAUNCH_L(ae_pull_kernel, a.L, chunk_grid(a.N), st, a);
+namespace {
+template <bool FAULTS>
+void ae_pull_l(const AeFArgs& f, hipStream_t st) {
+  const AeK<FAULTS>& a = f;
+  const uint32_t g = chunk_grid(a.N);
+  switch (a.L) {
+    case 1: ae_pull_kernel<1, FAULTS><<<g, kAeBlock, 0, st>>>(a); break;
+    case 2: ae_pull_kernel<2, FAULTS><<<g, kAeBlock, 0, st>>>(a); break;
+    case 4: ae_pull_kernel<4, FAULTS><<<g, kAeBlock, 0, st>>>(a); break;
+    case 8: ae_pull_kernel<8, FAULTS><<<g, kAeBlock, 0, st>>>(a); break;
+    case 16: ae_pull_kernel<16, FAULTS><<<g, kAeBlock, 0, st>>>(a); break;
+    case 32: ae_pull_kernel<32, FAULTS><<<g, kAeBlock, 0, st>>>(a); break;
+    default: ae_pull_kernel<64, FAULTS><<<g, kAeBlock, 0, st>>>(a); break;
+  }
+}
+
+// the emit of a binned round: NT tile counters, grid eg; k == 1 with full regions keeps the peers
+template <uint32_t NT, bool FAULTS>
+void ae_emit(const AeFArgs& f, uint32_t eg, hipStream_t st) {
+  const AeK<FAULTS>& a = f;
+  if (a.k == 1 && (1u << a.brs) == kAeBinRec)
+    ae_bin_emit_kernel<true, NT, FAULTS><<<eg, kAeBinThreads, 0, st>>>(a);
+  else
+    ae_bin_emit_kernel<false, NT, FAULTS><<<eg, kAeBinThreads, 0, st>>>(a);
+}
+
+template <bool FAULTS>
+void ae_dense_apply(const AeFArgs& f, hipStream_t st) {
+  const AeK<FAULTS>& a = f;
+#define AE_DENSE_L(KJ)                                                                         \
+  switch (a.L) {                                                                               \
+    case 1: ae_dense_apply_kernel<1, KJ, FAULTS><<<a.bnt, kAeDThreads, 0, st>>>(a); break;     \
+    case 2: ae_dense_apply_kernel<2, KJ, FAULTS><<<a.bnt, kAeDThreads, 0, st>>>(a); break;     \
+    case 4: ae_dense_apply_kernel<4, KJ, FAULTS><<<a.bnt, kAeDThreads, 0, st>>>(a); break;     \
+    case 8: ae_dense_apply_kernel<8, KJ, FAULTS><<<a.bnt, kAeDThreads, 0, st>>>(a); break;     \
+    default: ae_dense_apply_kernel<16, KJ, FAULTS><<<a.bnt, kAeDThreads, 0, st>>>(a); break;   \
+  }
+  if (a.K == 16) {  // 16-B row pieces
+    if (a.k == 1) ae_dense_apply_q_kernel<1, FAULTS><<<a.bnt, kAeQThreads, 0, st>>>(a);
+    else if (a.k == 2) ae_dense_apply_q_kernel<2, FAULTS><<<a.bnt, kAeQThreads, 0, st>>>(a);
+    else ae_dense_apply_q_kernel<3, FAULTS><<<a.bnt, kAeQThreads, 0, st>>>(a);
+  } else if (a.k == 1) {
+    AE_DENSE_L(1)
+  } else if (a.k == 2) {
+    AE_DENSE_L(2)
+  } else {
+    AE_DENSE_L(3)
+  }
+#undef AE_DENSE_L
+}
+}  // namespace
+
+hipError_t launch_ae_round(const AeFArgs& a, hipStream_t st) {
+  if (a.fa.any()) ae_pull_l<true>(a, st);
+  else ae_pull_l<false>(a, st);
   AE_LAUNCH_L(ae_push_kernel, a.L, chunk_grid(a.N), st, a);
   return hipGetLastError();
 }
@@ -1323,8 +1425,9 @@ hipError_t launch_ae_stats(const AeArgs& a, const uint32_t* V, uint64_t* ab, boo
   return hipGetLastError();
 }
 
-hipError_t launch_ae_sparse(const AeArgs& a, hipStream_t st) {
-  ae_sparse_scan_kernel<<<a.nseg, kAeBlock, 0, st>>>(a);
+hipError_t launch_ae_sparse(const AeFArgs& a, hipStream_t st) {
+  if (a.fa.any()) ae_sparse_scan_kernel<true><<<a.nseg, kAeBlock, 0, st>>>(a);
+  else ae_sparse_scan_kernel<false><<<a.nseg, kAeBlock, 0, st>>>(static_cast<const AeArgs&>(a));
   AE_LAUNCH_L(ae_sparse_gather_kernel, a.L, a.nseg * a.spb, st, a);
   AE_LAUNCH_L(ae_sparse_apply_kernel, a.L, a.nseg * a.spb, st, a);
   AE_LAUNCH_L(ae_sparse_fix_kernel, a.L, a.nseg * a.spb, st, a);
@@ -1348,12 +1451,10 @@ AeBinGeom ae_bin_geom(uint64_t N, uint32_t k) {
 
 bool ae_bin_fits(const AeBinGeom& g) { return g.nt <= kAeBinTiles; }
 
-hipError_t launch_ae_sparse_binned(const AeArgs& a, hipStream_t st) {
+hipError_t launch_ae_sparse_binned(const AeFArgs& a, hipStream_t st) {
   const uint32_t eg = a.bnreg < 512 ? a.bnreg : 512;  // two blocks per CU
-  if (a.k == 1 && (1u << a.brs) == kAeBinRec)
-    ae_bin_emit_kernel<true, kAeBinTiles><<<eg, kAeBinThreads, 0, st>>>(a);
-  else
-    ae_bin_emit_kernel<false, kAeBinTiles><<<eg, kAeBinThreads, 0, st>>>(a);
+  if (a.fa.any()) ae_emit<kAeBinTiles, true>(a, eg, st);
+  else ae_emit<kAeBinTiles, false>(a, eg, st);
   ae_bin_scan_kernel<<<a.bnt, kAeBinThreads, 0, st>>>(a);
   AE_LAUNCH_L(ae_sparse_gather_kernel, a.L, a.nseg * a.spb, st, a);
   AE_LAUNCH_L(ae_sparse_apply_kernel, a.L, a.nseg * a.spb, st, a);
@@ -1374,32 +1475,15 @@ bool ae_dense_fits(const AeBinGeom& g, uint64_t N, uint32_t k, uint32_t K) {
   return g.nt <= kAeDTiles && g.nreg <= kAeDMaxReg && N <= (1ull << 26) && k <= 3 && K <= 16;
 }
 
-hipError_t launch_ae_dense_binned(const AeArgs& a, hipStream_t st) {
+hipError_t launch_ae_dense_binned(const AeFArgs& a, hipStream_t st) {
   const uint32_t eg = a.bnreg < 256 ? a.bnreg : 256;  // one block per CU (LDS)
-  if (a.k == 1 && (1u << a.brs) == kAeBinRec)
-    ae_bin_emit_kernel<true, kAeDTiles><<<eg, kAeBinThreads, 0, st>>>(a);
-  else
-    ae_bin_emit_kernel<false, kAeDTiles><<<eg, kAeBinThreads, 0, st>>>(a);
-#define AE_DENSE_L(KJ)                                                                 \
-  switch (a.L) {                                                                       \
-    case 1: ae_dense_apply_kernel<1, KJ><<<a.bnt, kAeDThreads, 0, st>>>(a); break;     \
-    case 2: ae_dense_apply_kernel<2, KJ><<<a.bnt, kAeDThreads, 0, st>>>(a); break;     \
-    case 4: ae_dense_apply_kernel<4, KJ><<<a.bnt, kAeDThreads, 0, st>>>(a); break;     \
-    case 8: ae_dense_apply_kernel<8, KJ><<<a.bnt, kAeDThreads, 0, st>>>(a); break;     \
-    default: ae_dense_apply_kernel<16, KJ><<<a.bnt, kAeDThreads, 0, st>>>(a); break;   \
-  }
-  if (a.K == 16) {  // 16-B row pieces
-    if (a.k == 1) ae_dense_apply_q_kernel<1><<<a.bnt, kAeQThreads, 0, st>>>(a);
-    else if (a.k == 2) ae_dense_apply_q_kernel<2><<<a.bnt, kAeQThreads, 0, st>>>(a);
-    else ae_dense_apply_q_kernel<3><<<a.bnt, kAeQThreads, 0, st>>>(a);
-  } else if (a.k == 1) {
-    AE_DENSE_L(1)
-  } else if (a.k == 2) {
-    AE_DENSE_L(2)
+  if (a.fa.any()) {
+    ae_emit<kAeDTiles, true>(a, eg, st);
+    ae_dense_apply<true>(a, st);
   } else {
-    AE_DENSE_L(3)
+    ae_emit<kAeDTiles, false>(a, eg, st);
+    ae_dense_apply<false>(a, st);
   }
-#undef AE_DENSE_L
   return hipGetLastError();
 }
 

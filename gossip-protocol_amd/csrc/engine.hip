@@ -415,8 +415,8 @@ void bind_slices(gossip_engine* e) {
   }
 }
 
-AeArgs make_ae_args(gossip_engine* e) {
-  AeArgs a{};
+AeFArgs make_ae_args(gossip_engine* e) {
+  AeFArgs a{};
   a.V = e->V;
   a.Vn = e->Vn;
   a.ab = e->alive;
@@ -450,6 +450,7 @@ AeArgs make_ae_args(gossip_engine* e) {
   a.bnreg = e->ae_bg.nreg;
   a.spb = std::max<uint32_t>(1, 4096 / e->ae_nseg);  // ~4096 blocks over the edge list
   a.epoch = e->ae_epoch;
+  a.fa = Faults{e->fa.loss, e->fa.parts, e->N};  // (no stall model: DESIGN.md §2.11)
   return a;
 }
 
@@ -862,7 +863,7 @@ int ae_place(gossip_engine* e) {
         break;  // no room for another trial: keep the best so far
       if (hipMemcpyAsync(c.V, e->V, vb, hipMemcpyDeviceToDevice, e->stream) != hipSuccess) rc = GOSSIP_EHIP;
     }
-    AeArgs d = make_ae_args(e);
+    AeFArgs d = make_ae_args(e);
     d.V = i ? c.V.get() : e->V.get();
     d.Vn = i ? c.Vn.get() : e->Vn.get();
     d.partial = part;
@@ -920,7 +921,7 @@ int ae_round(gossip_engine* e) {
       HIP_OK(e, hipMemsetAsync(e->ae_claim, 0, (size_t)e->N * 4, e->stream));
       e->ae_epoch = 1;
     }
-    AeArgs a = make_ae_args(e);
+    AeFArgs a = make_ae_args(e);
     if ((rc = timer_begin(e, 2))) return rc;
     if (e->ae_bin) {
       a.zero = e->partial_d;
@@ -944,10 +945,10 @@ int ae_round(gossip_engine* e) {
     }
   }
   if (!sparse) {
-    const AeArgs a = make_ae_args(e);
+    const AeFArgs a = make_ae_args(e);
     bool binned = dbin;
     if (binned) {  // in-edge gathers, stats fused (no timer-1 part)
-      AeArgs d = a;
+      AeFArgs d = a;
       d.zero = e->partial_d;
       d.nzero = nz;
       d.btl = e->ae_dg.tl;
@@ -1037,7 +1038,7 @@ int step_ae(gossip_engine* e, uint32_t max_rounds, gossip_round_stats_t* stats, 
         HIP_OK(e, hipMemsetAsync(e->ae_claim, 0, (size_t)e->N * 4, e->stream));
         e->ae_epoch = 1;
       }
-      AeArgs a = make_ae_args(e);
+      AeFArgs a = make_ae_args(e);
       a.ab = ab;
       a.abn = abn;
       a.t = e->t + i;
@@ -1244,6 +1245,7 @@ AexArgs make_aex_args(gossip_engine* e) {
   a.flags = e->cfg.flags;
   a.rw = e->aex_rw;
   a.pw = e->aex_pw;
+  a.fa = Faults{e->fa.loss, e->fa.parts, e->N};
   return a;
 }
 
@@ -1346,9 +1348,14 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
     return GOSSIP_EINVAL;
   }
   const bool faulty = cfg->edge_loss || cfg->partitions > 1 || cfg->stall_rounds;
-  if (faulty && (cfg->mode == GOSSIP_MODE_ANTIENTROPY || (cfg->mode == GOSSIP_MODE_FLOOD && G != 1))) {
-    g_create_error = "edge_loss / partitions / stall_rounds apply to the random modes and to one-shard FLOOD "
-                     "(ANTIENTROPY's fault model is churn)";
+  if (cfg->stall_rounds && cfg->mode == GOSSIP_MODE_ANTIENTROPY) {
+    g_create_error = "stall_rounds applies to the random modes and to one-shard FLOOD (ANTIENTROPY has no "
+                     "per-neighbour deadline: its fault model is churn, edge_loss and partitions)";
+    return GOSSIP_ENOTSUP;
+  }
+  if (faulty && cfg->mode == GOSSIP_MODE_FLOOD && G != 1) {
+    g_create_error = "edge_loss / partitions / stall_rounds apply to the random modes, ANTIENTROPY (no stall_rounds) "
+                     "and one-shard FLOOD";
     return GOSSIP_ENOTSUP;
   }
   int ndev = 0;
@@ -2514,10 +2521,9 @@ int gossip_ae_finish(gossip_engine_t* e, uint64_t* partial) {
 
 int gossip_set_faults(gossip_engine_t* e, uint32_t edge_loss, uint32_t partitions) {
   if (!e) return GOSSIP_EINVAL;
-  if ((edge_loss || partitions > 1) &&
-      (e->mode == GOSSIP_MODE_ANTIENTROPY || (e->mode == GOSSIP_MODE_FLOOD && !e->flood_edges)))
-    return e->fail(GOSSIP_ENOTSUP, "faults: random modes, or a FLOOD engine created with faults or stall_rounds "
-                                   "(its per-edge retry state)");
+  if ((edge_loss || partitions > 1) && e->mode == GOSSIP_MODE_FLOOD && !e->flood_edges)
+    return e->fail(GOSSIP_ENOTSUP, "faults: random modes, ANTIENTROPY, or a FLOOD engine created with faults or "
+                                   "stall_rounds (its per-edge retry state)");
   e->fa = Faults{edge_loss, partitions, e->N, e->stall_d, e->cfg.stall_rounds};
   e->pl.edge_loss = edge_loss, e->pl.partitions = partitions;
   return GOSSIP_OK;
@@ -2679,7 +2685,7 @@ int gossip_state_hash(gossip_engine_t* e, uint64_t* out) {
     return GOSSIP_OK;
   }
   if (e->mode == GOSSIP_MODE_ANTIENTROPY) {  // the stats kernel's hash of the current rows
-    AeArgs a = make_ae_args(e);
+    AeFArgs a = make_ae_args(e);
     a.flags |= GOSSIP_FLAG_HASH;
     HIP_OK(e, hipMemsetAsync(e->partial_d, 0, part_len(e) * 8, e->stream));
     HIP_OK(e, launch_ae_stats(a, e->V, e->alive, false, e->stream));

@@ -170,7 +170,8 @@ class AbiEngine:
         self._check(self._fn("set_param")(self._h, name.encode(), C.c_double(value)))
 
     def set_faults(self, edge_loss: int = 0, partitions: int = 0):
-        """Fault model for the following rounds."""
+        """Fault model for the following rounds (ANTIENTROPY: §2.11).  Sharded engines:
+        set the same values on every rank."""
         self._check(self._fn("set_faults")(self._h, edge_loss, partitions))
 
     def reset(self):

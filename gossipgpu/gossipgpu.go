@@ -84,8 +84,8 @@ type Config struct {
 	ShardCount   uint32 // 0 or 1: one engine holds every node
 	ChurnFail    uint32 // ANTIENTROPY churn
 	ChurnRecover uint32
-	EdgeLoss     uint32 // fault model (DESIGN.md §2.8)
-	Partitions   uint32
+	EdgeLoss     uint32 // fault model (DESIGN.md §2.8): random modes, FLOOD and ANTIENTROPY (§2.11)
+	Partitions   uint32 // ANTIENTROPY: no convergence while a partition stands (the target is global)
 	StallRounds  uint32 // the reference's expired-context stall (DESIGN.md §2.9), 0 = off
 }
 
@@ -267,6 +267,9 @@ func (e *Engine) InjectRandom() error {
 }
 
 // SetFaults changes the fault model between steps (e.g. heal a partition with parts = 0).
+// It applies to the random modes, to FLOOD engines created with faults and to ANTIENTROPY
+// (DESIGN.md §2.11: partition, let the sides diverge, heal, converge); on sharded engines
+// every rank sets the same values.
 func (e *Engine) SetFaults(edgeLoss, partitions uint32) error {
 	e.mu.Lock()
 	defer e.mu.Unlock()

@@ -96,10 +96,14 @@ typedef struct gossip_config {
   uint32_t shard_count; /* G >= 1, Nl = ceil(N/G)                                     */
   uint32_t churn_fail;    /* ANTIENTROPY: P(alive -> dead) per round, as x / 2^32      */
   uint32_t churn_recover; /* ANTIENTROPY: P(dead -> alive) per round, as x / 2^32      */
-  uint32_t edge_loss;   /* random modes: P(an edge's exchange is lost) per round, x / 2^32
-                           (the reference's lossy SyncRPC, main.go:77-87) */
-  uint32_t partitions;  /* random modes and FLOOD: 0/1 = none, P > 1 = nodes split into P
-                           contiguous blocks that cannot reach each other               */
+  uint32_t edge_loss;   /* random modes, FLOOD and ANTIENTROPY: P(an edge's exchange is lost)
+                           per round, x / 2^32 (the reference's lossy SyncRPC,
+                           main.go:77-87).  ANTIENTROPY (§2.11): a lost exchange moves neither
+                           end's row and is not counted in stats.messages                */
+  uint32_t partitions;  /* random modes, FLOOD and ANTIENTROPY: 0/1 = none, P > 1 = nodes split
+                           into P contiguous blocks that cannot reach each other.  ANTIENTROPY:
+                           the target stays the max over all nodes, so a run does not converge
+                           while a partition stands (gossip_step returns after max_rounds)  */
   uint32_t stall_rounds; /* 0 = off.  D > 0: the reference's deadline stall (DESIGN.md §2.9,
                            main.go:72-87: one 2 s context per neighbour, retried forever
                            once it expired).  FLOOD: a node forwards each value down its
@@ -107,7 +111,8 @@ typedef struct gossip_config {
                            neighbours; after D lost attempts on one neighbour the walk
                            never moves past it (D = 1: the reference under silent drops).
                            Random modes: a node whose exchanges were lost in D rounds in a
-                           row stops initiating exchanges until reset.  <= 16.           */
+                           row stops initiating exchanges until reset.  <= 16.
+                           ANTIENTROPY has no per-neighbour deadline: GOSSIP_ENOTSUP.    */
 } gossip_config_t;
 
 /* Stats of one round t: they describe S_{t+1}, the state the round produced. */
@@ -224,7 +229,9 @@ int gossip_inject_random(gossip_engine_t* eng);
 
 /* Fault model for the rounds that follow: same meaning as the config fields;
  * e.g. heal a partition between steps with partitions = 0.  FLOOD with faults
- * retries undelivered values every round (one shard only). */
+ * retries undelivered values every round (one shard only).
+ * ANTIENTROPY (§2.11): takes effect in the next round; rows, alive bits and the
+ * round index stay.  Sharded engines: set the same values on every rank. */
 int gossip_set_faults(gossip_engine_t* eng, uint32_t edge_loss, uint32_t partitions);
 
 /* Runs rounds until converged (FLOOD also: a round that sends nothing) or max_rounds
