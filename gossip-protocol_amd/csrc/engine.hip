@@ -2352,8 +2352,9 @@ int gossip_xd_serve(gossip_engine_t* e, void** replies) {
   if (int rc = timer_begin(e, 0)) return rc;
   HIP_OK(e, launch_xd_serve(e->xg, e->xb, e->S, e->xd_nin, e->R, e->stream));
   if (int rc = timer_end(e, 0)) return rc;
-  if (!e->driven && !e->ordered) HIP_OK(e, hipStreamSynchronize(e->stream));
-  if (int rc = timer_collect(e, false)) return rc;
+  // (timing mode syncs also under the library's driver and ordered collectives: the timers are
+  // folded here, and an event still in flight has no elapsed time)
+  if (int rc = pub_ready(e, true, false)) return rc;
   *replies = e->xb.rep_out;
   return GOSSIP_OK;
 }

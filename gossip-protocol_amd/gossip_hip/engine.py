@@ -484,7 +484,12 @@ class Engine(AbiEngine):
 
     def plan_model(self):
         """The planner's model of the sharded rounds it planned (gossip_plan_model): (modelled per-rank
-        ms since reset_timing, its link part, rounds covered, the current run's plan string)."""
+        ms since reset_timing, its link part, rounds covered, the current run's plan string).  The
+        string has one letter per planned round since round 0 (it restarts after reset), "DSAXCRrQ"[kind]:
+        D 0 state all-gather, S 1 sparse, A 2 ANTIENTROPY, X 3 exchange, C 4 class-coded, R 5 / r 6 / Q 7
+        replicated after the state all-gather / with no collective / after the class-coded all-gather
+        (gossip_hip.sharded.KIND_LETTERS).  Sharded ANTIENTROPY and multi-word shards do not plan and
+        add no letter."""
         ms, link, n = C.c_double(), C.c_double(), C.c_uint64()
         buf = C.create_string_buffer(256)
         self._check(self._fn("plan_model")(self._h, C.byref(ms), C.byref(link), C.byref(n), buf, C.c_uint32(256)))

@@ -539,7 +539,11 @@ func (e *Engine) RoundWall(cls uint32) (float64, uint64, uint64, error) {
 
 // PlanModel returns the planner's model of the sharded rounds it planned (gossip_plan_model):
 // modelled per-rank ms and their link part since ResetTiming, the rounds covered, and the current
-// run's plan string (S sparse, X exchange, C class-coded, D state all-gather).
+// run's plan string: one letter per planned round since round 0 (it restarts after Reset), the
+// letter of plan kind i being "DSAXCRrQ"[i] (D 0 state all-gather, S 1 sparse, A 2 ANTIENTROPY,
+// X 3 exchange, C 4 class-coded, R 5 / r 6 / Q 7 replicated after the state all-gather / with no
+// collective / after the class-coded all-gather).  Sharded ANTIENTROPY and multi-word shards do
+// not plan and add no letter.
 func (e *Engine) PlanModel() (float64, float64, uint64, string, error) {
 	var ms, link C.double
 	var n C.uint64_t

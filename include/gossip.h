@@ -327,9 +327,15 @@ int gossip_round_wall(const gossip_engine_t* eng, uint32_t cls, double* total_ms
 /* G > 1 random modes (either driver: the library's or a host's own collectives): the planner's
  * model of the rounds it planned (ABI v10) — the modelled per-rank ms (device time
  * from the measured rates plus link bytes over link_gbps x min(G - 1, 7) xGMI links) and its link
- * part, summed since gossip_reset_timing, the rounds they cover, and the current run's plan (one
- * letter per round since round 0: S sparse, X exchange, C class-coded, D state all-gather) in
- * plan[0 .. cap), NUL-terminated.  A measured N-GPU run can be set against it round for round. */
+ * part, summed since gossip_reset_timing, the rounds they cover, and the current run's plan in
+ * plan[0 .. cap), NUL-terminated: one letter per planned round since round 0 (the string restarts
+ * there after gossip_reset), the letter of gossip_sharded_plan's kind i being "DSAXCRrQ"[i]:
+ *   D 0 state all-gather      S 1 sparse                 A 2 ANTIENTROPY      X 3 exchange
+ *   C 4 class-coded           R 5 replicated after the state all-gather
+ *   r 6 replicated, no collective                        Q 7 replicated after the class-coded all-gather
+ * Engines that do not plan add no letter: sharded ANTIENTROPY (every round is kind 2, so A is
+ * reserved) and multi-word shards (every round is kind 0).  A measured N-GPU run can be set against
+ * the plan round for round. */
 int gossip_plan_model(const gossip_engine_t* eng, double* model_ms, double* link_ms, uint64_t* rounds, char* plan,
                       uint32_t cap);
 

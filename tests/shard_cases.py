@@ -1,28 +1,37 @@
-"""Sharded-round cases shared by test_shard_states.py (CPU, oracle host shards),
-test_gpu_shard_states.py and test_gpu_shard_wire.py (HIP shards on one device).  A plain module in
-the style of states.py and ae_cases.py: tables and helpers, no tests.
+"""Sharded-round cases shared by test_shard_states.py and test_shard_drivers.py (CPU, oracle host
+shards), test_gpu_shard_states.py and test_gpu_shard_wire.py (HIP shards on one device, the Python
+round bodies with the copy comm), test_gpu_group_states.py (the library's own driver, csrc/multi.hip)
+and test_gpu_shard_devvalues.py (the device-value calls with no sync).  A plain module in the style
+of states.py and ae_cases.py: tables and helpers, no tests.
 
   SLOTS / SLOTS_CC   the 8-slot plan carousel: every slot sets all six plan knobs, so a round's kind
                      is a function of the table and of what ran before it (expected_kinds);
   RUNS / PHILOX      the carousel runs, taken from test_state_builders.ROUNDS (hand-built states of
                      N0 nodes) plus one Philox run with shards of more than one 16384-node tile;
+  LockstepDriver, GroupDriver, OrderedDevDriver
+                     who runs a round: sharded._round with the copy comm, gossip_group_step, or
+                     sharded._round with OrderedDevComm (every copy a torch op on the engines' stream,
+                     counts and partials through the *_dev calls, no sync in the comm);
   RecordingComm      the copy comm of gossip_hip.sharded with a copy of every collective's send
-                     buffers, counts and receive buffers, per rank;
+                     buffers, counts and receive buffers, per rank (RecordingOrderedComm: the same
+                     over OrderedDevComm);
   wire / ref_wire    what a round put on the wire, normalised, and the same from S_t alone in numpy
                      (peers and lost edges from oracle/numpy_ref.py; the oracle's sharded code is
                      not used there: it is the second check).
 
 Every reference is exact: the comparisons have no tolerance.
 """
+import collections
 import functools
 
 import numpy as np
+import torch
 
 import numpy_ref as nr
 import oracle_py as op
 import states as st
 from gossip_hip import sharded
-from gossip_hip.engine import loss_threshold
+from gossip_hip.engine import Group, loss_threshold
 from gossip_hip.sharded import (CLASSCODED, DENSE, EXCHANGE, REP, REP_CLASSCODED, REP_GATHER, SPARSE, _CopyComm,
                                 _width)
 from states import N0, SEED
@@ -113,21 +122,32 @@ def close_all(engines):
 
 
 @functools.lru_cache(maxsize=None)
-def reference(run):
-    """One oracle engine over a run, a round at a time until it converges (at most 64 rounds):
-    (S_0 .. S_T as read-only [N] uint64 arrays, the per-round stats).  Computed once, shared."""
+def _reference(run):
     (ref,) = make_engines(op.OracleEngine, run, 1)
-    states, stats = [ref.read_shard()[0].copy()], []
+    states, stats, infected = [ref.read_shard()[0].copy()], [], []
     for _ in range(64):
         res = ref.step(1)
         stats.append(res.stats[0])
+        infected.append(res.infected[0].copy())
         states.append(ref.read_shard()[0].copy())
         if res.converged:
             break
-    for s in states:
+    for s in states + infected:
         s.setflags(write=False)
     assert len(stats) == ROUNDS.get(run, len(stats))
-    return tuple(states), tuple(stats)
+    return tuple(states), tuple(stats), tuple(infected)
+
+
+def reference(run):
+    """One oracle engine over a run, a round at a time until it converges (at most 64 rounds):
+    (S_0 .. S_T as read-only [N] uint64 arrays, the per-round stats).  Computed once, shared."""
+    return _reference(run)[:2]
+
+
+def reference_infected(run):
+    """The same run's per-rumor node counts after every round ([R] uint64 each), as gossip_step and
+    gossip_group_step hand them out beside the stats."""
+    return _reference(run)[2]
 
 
 # -- the carousel -----------------------------------------------------------------------------
@@ -162,18 +182,20 @@ def drive_round(engines, comm, kinds=None):
     return stats[0]
 
 
-def carousel(engines, table, offset, rounds, comm=None, after_round=None):
-    """`rounds` rounds (fewer if the run converges), round i with the knobs of slot offset + i.
-    after_round(i, kind, knobs): called after each round.  Returns (per-round stats, kinds)."""
-    comm = comm or _CopyComm(engines)
+def carousel(driver, table, offset, rounds, after_round=None):
+    """`rounds` rounds (fewer if the run converges), round i with the knobs of slot offset + i set on
+    every shard.  after_round(i, kind, knobs): called after each round.  Returns (per-round stats,
+    kinds)."""
     stats, kinds = [], []
     for i in range(rounds):
         knobs = table[(offset + i) % len(table)][1]
-        set_knobs(engines, knobs)
-        stats.append(drive_round(engines, comm, kinds))
+        set_knobs(driver.engines, knobs)
+        st_, kind = driver.round()
+        stats.append(st_)
+        kinds.append(kind)
         if after_round is not None:
-            after_round(i, kinds[-1], knobs)
-        if stats[-1]["converged"]:
+            after_round(i, kind, knobs)
+        if st_["converged"]:
             break
     return stats, kinds
 
@@ -186,17 +208,81 @@ def assert_shards_hold(engines, state):
 
 # -- the recording comm -----------------------------------------------------------------------
 
-class RecordingComm(_CopyComm):
-    """The copy comm, keeping for every collective of a round a copy of what each rank sent, the
-    counts, and what each rank received: self.log has one entry per collective, in the order the round
-    body issued them, with per-rank payloads (uint64 words, uint32 for the exchange ids)."""
+class OrderedDevComm(_CopyComm):
+    """Stands in for RCCL's ordering on one device: every engine launches on torch's current stream
+    (OrderedDevDriver binds them), every slice copy is a torch op on that stream, and nothing here
+    synchronizes.  Counts and partials come from engine.<stem>_dev where the library has that form:
+    the published device values are combined on the device and read with one .cpu(), the only host
+    wait of that exchange (as in gossip_hip.sharded._Comm.dev_*).  Host engines (the oracle's) have
+    no *_dev calls and take the host forms, so the comm can be rehearsed on the CPU.  self.called
+    counts the engine calls made, by name (stem + "_dev" or the bare stem)."""
+
+    direct = True
+
+    def __init__(self, engines):
+        super().__init__(engines)
+        self.called = collections.Counter()
+
+    def _sync(self):  # never: the copies and the engines' kernels are ordered by the one stream
+        pass
+
+    def all_gather_async(self, recv, send, nbytes: int):
+        """Enqueued at once, before the engines' own-slice kernels (the order RCCL's launch has)."""
+        self.all_gather(recv, send, nbytes)
+        return None
+
+    def wait(self, work):
+        pass
+
+    def _values(self, L, stem, *args, each=None):
+        """(every engine's results, whether their last one is a pointer to device values)"""
+        dev = all(e.on_device and e.supports(stem + "_dev") for e in L)
+        name = stem + "_dev" if dev else stem
+        self.called[name] += 1
+        return sharded._calls(L, name, *args, each=each), dev
+
+    def _read(self, ptrs, n):
+        """[len(ptrs), n] int64 on the device from n values at each pointer (no host wait yet)"""
+        return torch.stack(self._views(ptrs, [n * 8] * len(ptrs)))
+
+    def gather_counts(self, L, stem: str):
+        res, dev = self._values(L, stem)
+        if not dev:
+            return [r[:-1] for r in res], [r[-1] for r in res]
+        counts = self._read([r[-1] for r in res], 1).cpu()
+        return [r[:-1] for r in res], [int(c) for c in counts[:, 0]]
+
+    def exchange_counts(self, L, stem: str, *args):
+        res, dev = self._values(L, stem, *args)
+        if dev:
+            counts = [[int(c) for c in row] for row in self._read([r[-1] for r in res], self.world).cpu()]
+        else:
+            counts = [[int(c) for c in r[-1]] for r in res]
+        return [r[:-1] for r in res], counts, [[c[r] for c in counts] for r in range(self.world)]
+
+    def sum(self, L, stem: str, each=None) -> np.ndarray:
+        parts, dev = self._values(L, stem, each=each)
+        if dev:  # the all-reduce: an int64 sum on the device wraps like RCCL's
+            return self._read(parts, L[0].partial_len()).sum(dim=0).cpu().numpy().view(np.uint64)
+        tot = np.zeros_like(parts[0])
+        for p in parts:
+            tot = tot + p
+        return tot
+
+
+class _Recording:
+    """Mixin over a copy comm, keeping for every collective of a round a copy of what each rank sent,
+    the counts, and what each rank received: self.log has one entry per collective, in the order the
+    round body issued them, with per-rank payloads (uint64 words, uint32 for the exchange ids).  It
+    waits for the device before it copies a buffer (it records); the comm under it is left as it is."""
 
     def __init__(self, engines):
         super().__init__(engines)
         self.log = []
 
     def _grab(self, ptrs, nbytes, width=8):
-        self._sync()
+        for d in {e.device for e in self.engines if e.on_device}:
+            torch.cuda.synchronize(d)
         ut = np.uint64 if width == 8 else np.uint32
         return [v.cpu().numpy().copy().view(ut) for v in self._views(ptrs, nbytes, width)]
 
@@ -228,6 +314,155 @@ class RecordingComm(_CopyComm):
         head, counts, in_counts = super().exchange_counts(L, stem, *args)
         self.log.append(dict(op="counts", stem=stem, counts=[list(c) for c in counts]))
         return head, counts, in_counts
+
+
+class RecordingComm(_Recording, _CopyComm):
+    """The recording copy comm of gossip_hip.sharded."""
+
+
+class RecordingOrderedComm(_Recording, OrderedDevComm):
+    """The recording comm over the device-value path."""
+
+
+# -- who runs a round -------------------------------------------------------------------------
+# A driver has `engines` (the shard views: inject, set_param, set_faults, reset, read_shard,
+# state_hash), round() -> (the stats every shard agreed on, the round's kind), close(), and
+# `infected`: the per-rumor counts of the last round where the driver hands them out, else None.
+# Every driver is made as driver(factory, N, R, mode, k, seed, G, flags=, params=, **faults) with
+# its shards empty; the bodies build the state through `engines`.
+
+PLAN_LETTERS = "DSAXCRrQ"  # csrc/engine.hip gossip_sharded_plan: the plan string's letter of kind i
+
+
+class LockstepDriver:
+    """The product's round bodies (sharded._round) over the copy comm, on shards made by `factory`
+    (Engine or op.OracleEngine)."""
+
+    comm_class, recording_class = _CopyComm, RecordingComm
+    infected = None
+
+    def __init__(self, factory, N, R, mode, k, seed, G, flags=0, params=None, recording=False, **faults):
+        self.engines = [factory(N, R, mode, k, seed, flags=flags, shard_rank=r, shard_count=G, params=params, **faults)
+                        for r in range(G)]
+        self.comm = (self.recording_class if recording else self.comm_class)(self.engines)
+
+    def round(self):
+        kinds = []
+        stats = drive_round(self.engines, self.comm, kinds)
+        return stats, kinds[0]
+
+    def close(self):
+        close_all(self.engines)
+
+
+class OrderedDevDriver(LockstepDriver):
+    """The same round bodies over OrderedDevComm: device engines are bound to torch's current stream
+    and run with ordered_collectives = 1 for the duration of each round (as sharded_round does for
+    RCCL), so no call of the round synchronizes to publish a buffer or a value.  Host engines run
+    unbound: the rehearsal of the comm on the CPU."""
+
+    comm_class, recording_class = OrderedDevComm, RecordingOrderedComm
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.device_engines = [e for e in self.engines if e.on_device]
+        self.ordered = {}  # engine rank -> the last ordered_collectives value this driver set
+
+    def _ordered(self, value):
+        for e in self.device_engines:
+            e.set_param("ordered_collectives", value)
+            self.ordered[e.cfg.shard_rank] = value
+
+    def round(self):
+        for e in self.device_engines:
+            e.set_stream(torch.cuda.current_stream().cuda_stream)
+        self._ordered(1)
+        try:
+            return super().round()
+        finally:  # the flag must not outlive the round that bound the stream
+            self._ordered(0)
+
+    def release(self):
+        """Hands the engines back to a host driver: no flag left, bound to the null stream."""
+        self._ordered(0)
+        for e in self.device_engines:
+            e.set_stream(0)
+
+    def close(self):
+        self.release()
+        super().close()
+
+
+class GroupDriver:
+    """The library's own driver (csrc/multi.hip behind gossip_group_step): a gossip_hip.Group of G
+    shards on device 0 over the copy transport, a round = group.step(1).  The kind of the round just
+    run is the last letter of every shard's plan string (gossip_plan_model; the string restarts at
+    round 0 after a reset, so only its last letter is read), and every shard's count of planned
+    rounds must have gone up by one, so a stale letter cannot pass.  Multi-word shards have no
+    planner (every round is the state all-gather): their plan string stays empty."""
+
+    def __init__(self, factory, N, R, mode, k, seed, G, flags=0, params=None, **faults):
+        assert factory is None, "the group makes its own engines"
+        self.group = Group(N, R, mode, k, seed, flags=flags, n_shards=G, devices=[0] * G, transport=2, params=params,
+                           **faults)
+        assert self.group.transport == 2
+        self.engines = self.group.shards
+        self.infected = None
+        self.planned = [e.plan_model()[2] for e in self.engines]
+
+    def _kind(self):
+        models = [e.plan_model() for e in self.engines]
+        if self.engines[0].n_words > 1:
+            assert all(m[2] == 0 and m[3] == "" for m in models)
+            return DENSE
+        planned = [m[2] for m in models]
+        assert planned == [p + 1 for p in self.planned], "not one planned round per shard"
+        self.planned = planned
+        letters = {m[3][-1] for m in models}
+        assert len(letters) == 1, f"shards report different kinds: {letters}"
+        return PLAN_LETTERS.index(letters.pop())
+
+    def round(self):
+        res = self.group.step(1)
+        assert res.rounds == 1
+        self.infected = res.infected[0]
+        return res.stats[0], self._kind()
+
+    def close(self):
+        self.group.close()
+
+
+def open_driver(driver, factory, run, G, flags=0, params=None, **kw):
+    """The driver (None: LockstepDriver) over the G shards of a run, built."""
+    _, mode, k, loss, parts = run
+    N, R = run_shape(run)
+    d = (driver or LockstepDriver)(factory, N, R, mode, k, SEED, G, flags=1 | flags, params=params, edge_loss=loss,
+                                   partitions=parts, **kw)
+    try:
+        for e in d.engines:
+            build_state(e, run)
+    except BaseException:
+        d.close()
+        raise
+    return d
+
+
+def run_to_convergence(driver, max_rounds):
+    """sharded.lockstep_run through a driver: (per-round stats, kinds)"""
+    stats, kinds = [], []
+    for _ in range(max_rounds):
+        st_, kind = driver.round()
+        stats.append(st_)
+        kinds.append(kind)
+        if st_["converged"]:
+            break
+    return stats, kinds
+
+
+def assert_infected(driver, want):
+    """the last round's per-rumor counts, where the driver hands them out"""
+    if driver.infected is not None:
+        assert np.array_equal(driver.infected, want), "per-rumor counts"
 
 
 def _sorted_rows(a, b):
@@ -522,63 +757,70 @@ def check_round_wire(kind, log, S, run, G, t, knobs):
 
 # -- test bodies shared by the CPU file (factory = op.OracleEngine) and the GPU files (Engine) ------
 
-def body_carousel(factory, run, G, offset, table=SLOTS, flags=0):
-    """Per-round stats, the kind sequence exactly as the table gives it, every shard's final state."""
+def body_carousel(factory, run, G, offset, table=SLOTS, flags=0, driver=None):
+    """Per-round stats (and per-rumor counts where the driver has them), the kind sequence exactly as
+    the table gives it, every shard's final state."""
     states, want = reference(run)
-    engines = make_engines(factory, run, G, flags)
+    infected = reference_infected(run)
+    d = open_driver(driver, factory, run, G, flags)
     try:
-        stats, kinds = carousel(engines, table, offset, len(want))
+        stats, kinds = carousel(d, table, offset, len(want),
+                                after_round=lambda i, kind, knobs: assert_infected(d, infected[i]))
         assert stats == list(want)
         assert kinds == expected_kinds(table, offset, len(want))
-        assert_shards_hold(engines, states[-1])
+        assert_shards_hold(d.engines, states[-1])
     finally:
-        close_all(engines)
+        d.close()
     return kinds
 
 
-def body_carousel_wire(factory, run, G, offset, other=None):
+def body_carousel_wire(factory, run, G, offset, other=None, driver=None):
     """Every wire product of every round against the numpy references; other: a second factory whose
-    shards run the same carousel, every product compared with theirs too (counts per owner included)."""
+    shards run the same carousel, every product compared with theirs too (counts per owner included).
+    driver: LockstepDriver (None) or OrderedDevDriver, made with its recording comm."""
     states, want = reference(run)
     N, _ = run_shape(run)
-    engines = make_engines(factory, run, G)
+    d = open_driver(driver, factory, run, G, recording=True)
     theirs = make_engines(other, run, G) if other else None
     try:
-        comm = RecordingComm(engines)
+        comm = d.comm
         comm2 = RecordingComm(theirs) if other else None
         stats = []
         for i in range(len(want)):
             knobs = SLOTS[(offset + i) % len(SLOTS)][1]
-            kinds = []
-            set_knobs(engines, knobs)
-            stats.append(drive_round(engines, comm, kinds))
-            got = check_round_wire(kinds[0], comm.take(), states[i], run, G, i, knobs)
+            set_knobs(d.engines, knobs)
+            st_, kind = d.round()
+            stats.append(st_)
+            got = check_round_wire(kind, comm.take(), states[i], run, G, i, knobs)
             if other:
                 kinds2 = []
                 set_knobs(theirs, knobs)
-                assert drive_round(theirs, comm2, kinds2) == stats[-1] and kinds2 == kinds
-                assert_wire_equal(kinds[0], got, wire(kinds[0], comm2.take()), N, G)
+                assert drive_round(theirs, comm2, kinds2) == stats[-1] and kinds2 == [kind]
+                assert_wire_equal(kind, got, wire(kind, comm2.take()), N, G)
         assert stats == list(want)
     finally:
-        close_all(engines + (theirs or []))
+        d.close()
+        close_all(theirs or [])
 
 
-def body_forced_kind(factory, run, knobs, kind, G=4):
+def body_forced_kind(factory, run, knobs, kind, G=4, driver=None):
     """A built state before any round under one forced plan: the first round is of that kind and equals
     the oracle, then the run goes to convergence."""
     states, want = reference(run)
-    engines = make_engines(factory, run, G, params=knobs)
+    infected = reference_infected(run)
+    d = open_driver(driver, factory, run, G, params=knobs)
     try:
-        kinds = []
-        assert drive_round(engines, _CopyComm(engines), kinds) == want[0] and kinds == [kind]
-        assert_shards_hold(engines, states[1])
+        assert d.round() == (want[0], kind)
+        assert_infected(d, infected[0])
+        assert_shards_hold(d.engines, states[1])
         if len(want) > 1:
-            stats, kinds = sharded.lockstep_run(engines, 64)
+            stats, kinds = run_to_convergence(d, 64)
             assert stats == list(want[1:])
+            assert_infected(d, infected[-1])
             assert set(kinds) == {REP if kind == REP_GATHER else kind}
-        assert_shards_hold(engines, states[-1])
+        assert_shards_hold(d.engines, states[-1])
     finally:
-        close_all(engines)
+        d.close()
 
 
 REP_PARAMS = {"sparse_frac": -1, "replicate": 1, "cc_frac": 0, "xd_shards": 0}
@@ -586,22 +828,26 @@ REP_KINDS = [5, 6, 6, 5, 6, 6, 6, 6, 6, 5, 6, 6]
 REP_RUN = RUNS[1]  # thirds, push, k = 1: 11 rounds to convergence, so no chunk runs on a full state
 
 
-def body_replicated_sequence(factory, params, G=4, want_kinds=None):
+def body_replicated_sequence(factory, params, G=4, want_kinds=None, driver=None):
     """3 rounds, eight injects, 2 rounds, set_faults(0.3, 5 partitions), 2 rounds, healed, 2 rounds, reset
-    and the thirds state again, 3 rounds: stats equal one oracle engine's after every chunk, every
-    shard is all zero with hash 0 right after the reset, the final states are equal, and the kinds so
-    far are want_kinds' after every chunk (None: whatever the engine plans)."""
+    and the thirds state again, 3 rounds: stats (and per-rumor counts where the driver has them) equal
+    one oracle engine's after every chunk, every shard is all zero with hash 0 right after the reset,
+    the final states are equal, and the kinds so far are want_kinds' after every chunk (None: whatever
+    the engine plans)."""
     (ref,) = make_engines(op.OracleEngine, REP_RUN, 1)
-    engines = make_engines(factory, REP_RUN, G, params=params)
-    everyone = [ref] + engines
+    d = open_driver(driver, factory, REP_RUN, G, params=params)
+    engines = d.engines
+    everyone = [ref] + list(engines)
     kinds = []
 
     def chunk(n, what):
-        want = [ref.step(1).stats[0] for _ in range(n)]
-        assert not any(s["converged"] for s in want)
-        comm = _CopyComm(engines)
-        got = [drive_round(engines, comm, kinds) for _ in range(n)]  # (lockstep_run stops at convergence)
-        assert got == want, what
+        for _ in range(n):  # (run_to_convergence would stop at convergence)
+            res = ref.step(1)
+            assert not res.converged
+            got, kind = d.round()
+            kinds.append(kind)
+            assert got == res.stats[0], what
+            assert_infected(d, res.infected[0])
         assert want_kinds is None or kinds == want_kinds[:len(kinds)], what
 
     try:
@@ -625,33 +871,38 @@ def body_replicated_sequence(factory, params, G=4, want_kinds=None):
         chunk(3, "after reset and rebuild")
         assert_shards_hold(engines, ref.read_shard()[0])
     finally:
-        close_all(engines)
+        d.close()
     return kinds
 
 
 @functools.lru_cache(maxsize=None)
 def multiword_reference(case):
+    """(per-round stats, the final [W, N] state, the per-round per-rumor counts) of one oracle engine"""
     N, R, mode, k, G, faults, rounds = MULTIWORD[case]
     ref = op.OracleEngine(N, R, mode, k, SEED, flags=1, **faults)
     ref.inject_random()
     res = ref.step(rounds or 64)
-    return res.stats, ref.read_shard()
+    return res.stats, ref.read_shard(), res.infected
 
 
-def body_multiword(factory, case):
+def body_multiword(factory, case, driver=None):
     """W > 1 sharded: every round the plain state all-gather, equal to one oracle engine; no bit at or
     above R in any shard after any round."""
     N, R, mode, k, G, faults, rounds = MULTIWORD[case]
-    want, full = multiword_reference(case)
+    want, full, infected = multiword_reference(case)
     assert bool(want[-1]["converged"]) == (rounds is None) and len(want) == (rounds or len(want))
-    engines = [factory(N, R, mode, k, SEED, flags=1, shard_rank=r, shard_count=G, **faults) for r in range(G)]
+    d = (driver or LockstepDriver)(factory, N, R, mode, k, SEED, G, flags=1, **faults)
+    engines = d.engines
     top = ~nr.full_masks(R)[-1]
     try:
         for e in engines:
             e.inject_random()
-        comm, kinds = _CopyComm(engines), []
-        for w in want:
-            assert drive_round(engines, comm, kinds) == w
+        kinds = []
+        for i, w in enumerate(want):
+            got, kind = d.round()
+            kinds.append(kind)
+            assert got == w
+            assert_infected(d, infected[i])
             for e in engines:
                 assert not (e.read_shard()[-1] & top).any()
         assert set(kinds) == {DENSE}
@@ -659,4 +910,4 @@ def body_multiword(factory, case):
             assert np.array_equal(e.read_shard(), full[:, e.lo:e.hi])
         return [e.hi - e.lo for e in engines]
     finally:
-        close_all(engines)
+        d.close()
