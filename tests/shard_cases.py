@@ -1,7 +1,8 @@
 """Sharded-round cases shared by test_shard_states.py and test_shard_drivers.py (CPU, oracle host
 shards), test_gpu_shard_states.py and test_gpu_shard_wire.py (HIP shards on one device, the Python
 round bodies with the copy comm), test_gpu_group_states.py (the library's own driver, csrc/multi.hip)
-and test_gpu_shard_devvalues.py (the device-value calls with no sync).  A plain module in the style
+and test_gpu_shard_devvalues.py (the device-value calls with no sync); WIDE, the shards of 16 and 64
+words per node, by test_wide_state.py and test_gpu_wide_state.py.  A plain module in the style
 of states.py and ae_cases.py: tables and helpers, no tests.
 
   SLOTS / SLOTS_CC   the 8-slot plan carousel: every slot sets all six plan knobs, so a round's kind
@@ -30,6 +31,7 @@ import torch
 import numpy_ref as nr
 import oracle_py as op
 import states as st
+import topologies as tp
 from gossip_hip import sharded
 from gossip_hip.engine import Group, loss_threshold
 from gossip_hip.sharded import (CLASSCODED, DENSE, EXCHANGE, REP, REP_CLASSCODED, REP_GATHER, SPARSE, _CopyComm,
@@ -83,6 +85,43 @@ MULTIWORD = [
     (30011, 65, "pushpull", 3, 3, dict(edge_loss=loss_threshold(0.1), partitions=3, stall_rounds=3), 12),
 ]
 MULTIWORD_IDS = [f"N{c[0]}-R{c[1]}-{c[2]}-G{c[4]}" for c in MULTIWORD]
+
+# wide multi-word shards (test_gpu_wide_state.py): the same tuple plus the workload, "random" (inject_random),
+# "sparse" (states.sparse_words: most words of every node empty) or "flood" (ragged rows, one value in each of
+# 200 slots spread over all words).  1024 rumors (W = 16) at G = 3 with a ragged Nl (1001, 1001, 999 nodes);
+# 4096 rumors (W = 64) at G = 5 with a ragged last shard (201 x 4 + 199) and with an empty one: only N < 20
+# leaves the fifth shard nothing (16 nodes: 4, 4, 4, 4, 0)
+WIDE_NODES = 3001
+WIDE = [
+    (WIDE_NODES, 1024, "push", 2, 3, {}, None, "random"),
+    (16, 4096, "pull", 1, 5, {}, None, "random"),
+    (1003, 4096, "pull", 3, 5, {}, 6, "sparse"),
+    (WIDE_NODES, 1024, "flood", 0, 3, {}, 9, "flood"),  # the ninth round sends nothing
+    (WIDE_NODES, 1024, "pushpull", 2, 3, dict(edge_loss=loss_threshold(0.2), partitions=3, stall_rounds=3), 10,
+     "sparse"),
+    (1003, 4096, "push", 2, 5, dict(edge_loss=loss_threshold(0.2), partitions=2, stall_rounds=2), 8, "random"),
+]
+WIDE_IDS = [f"N{c[0]}-R{c[1]}-{c[2]}-G{c[4]}-{c[7]}" + ("-faults" if c[5] else "") for c in WIDE]
+
+
+@functools.lru_cache(maxsize=None)
+def wide_topology():
+    """Symmetrised ragged rows over WIDE_NODES nodes: hubs of 40 entries at 1, 1025 and 2049, empty rows,
+    self-loops and repeated entries."""
+    return tp.symmetrize(*tp.ragged(WIDE_NODES, 7, hub_every=1024, hub_deg=40), WIDE_NODES)
+
+
+def fill_work(engine, work, R):
+    """Builds one engine's (or one shard's) state for a workload of WIDE."""
+    if work == "random":
+        engine.inject_random()
+    elif work == "sparse":
+        st.sparse_words(engine, R)
+    else:
+        engine.set_topology(wide_topology())
+        for i in range(200):
+            x = i * (R - 1) // 199
+            engine.inject((431 * x + 3) % engine.n_nodes, x)
 
 
 def run_id(run):
@@ -876,35 +915,47 @@ def body_replicated_sequence(factory, params, G=4, want_kinds=None, driver=None)
 
 
 @functools.lru_cache(maxsize=None)
-def multiword_reference(case):
+def multiword_reference(case, wide=False):
     """(per-round stats, the final [W, N] state, the per-round per-rumor counts) of one oracle engine"""
-    N, R, mode, k, G, faults, rounds = MULTIWORD[case]
+    N, R, mode, k, G, faults, rounds, work = (WIDE if wide else MULTIWORD)[case] + (() if wide else ("random",))
     ref = op.OracleEngine(N, R, mode, k, SEED, flags=1, **faults)
-    ref.inject_random()
+    fill_work(ref, work, R)
     res = ref.step(rounds or 64)
     return res.stats, ref.read_shard(), res.infected
 
 
-def body_multiword(factory, case, driver=None):
+def body_multiword(factory, case, driver=None, wide=False):
     """W > 1 sharded: every round the plain state all-gather, equal to one oracle engine; no bit at or
-    above R in any shard after any round."""
-    N, R, mode, k, G, faults, rounds = MULTIWORD[case]
-    want, full, infected = multiword_reference(case)
+    above R in any shard after any round.  wide: a case of WIDE, and after every round the per-rumor
+    counts of the shards' own words equal the oracle's."""
+    N, R, mode, k, G, faults, rounds, work = (WIDE if wide else MULTIWORD)[case] + (() if wide else ("random",))
+    want, full, infected = multiword_reference(case, wide)
     assert bool(want[-1]["converged"]) == (rounds is None) and len(want) == (rounds or len(want))
     d = (driver or LockstepDriver)(factory, N, R, mode, k, SEED, G, flags=1, **faults)
     engines = d.engines
     top = ~nr.full_masks(R)[-1]
     try:
         for e in engines:
-            e.inject_random()
+            fill_work(e, work, R)
+        if wide and hasattr(d, "comm"):  # a lockstep driver: the round's summed partials carry the shards' counts
+            comm_sum = d.comm.sum
+
+            def keep(L, stem, each=None):
+                total = comm_sum(L, stem, each=each)
+                d.infected = total[4:4 + R]
+                return total
+            d.comm.sum = keep
         kinds = []
         for i, w in enumerate(want):
             got, kind = d.round()
             kinds.append(kind)
             assert got == w
             assert_infected(d, infected[i])
-            for e in engines:
-                assert not (e.read_shard()[-1] & top).any()
+            shards = [e.read_shard() for e in engines]
+            for s in shards:
+                assert not (s[-1] & top).any()
+            if wide:
+                assert nr.stats_of(np.concatenate(shards, axis=1), R)[1] == [int(x) for x in infected[i]]
         assert set(kinds) == {DENSE}
         for e in engines:
             assert np.array_equal(e.read_shard(), full[:, e.lo:e.hi])

@@ -1,10 +1,11 @@
 """Hand-built states and round-path tables shared by test_state_builders.py (CPU),
-test_gpu_states.py and test_gpu_geometry.py.  A plain module, not a conftest.
+test_gpu_states.py and test_gpu_geometry.py, and the wide sparse workload of test_wide_state.py
+and test_gpu_wide_state.py.  A plain module, not a conftest.
 
 A builder is `build(engine, R) -> number of inject calls`; it only calls
 `engine.inject`, so the same call builds the CPU oracle and the HIP engine.
-Every builder is written for N0 nodes: one full 16384-node tile, one 64-node
-group and one node of a ragged last group.
+Every builder of BUILDERS is written for N0 nodes: one full 16384-node tile, one
+64-node group and one node of a ragged last group; sparse_words takes any size.
 """
 import numpy as np
 
@@ -87,6 +88,25 @@ def disjoint(engine, R=64):
     for n in range(N0):
         engine.inject(n, n % R)
     return N0
+
+
+def sparse_word_ids(R):
+    """The state words the `sparse_words` workload touches: the first, word 17 (the middle word of
+    a state with fewer) and the last."""
+    W = (R + 63) // 64
+    return sorted({0, 17 if W > 18 else W // 2, W - 1})
+
+
+def sparse_words(engine, R, N=None):
+    """Wide states (R > 64), any N: rumors in the words of sparse_word_ids only, every other word of
+    every node stays empty for good.  Per touched word its bits 0, 31 and 63 (those below R) and
+    rumor R - 1, each at three nodes; no node can ever be full, so runs take a fixed number of rounds."""
+    N = N or engine.n_nodes
+    rumors = sorted({64 * w + b for w in sparse_word_ids(R) for b in (0, 31, 63) if 64 * w + b < R} | {R - 1})
+    for r in rumors:
+        for i in range(3):
+            engine.inject((r * 2654435761 + i * 40503 + 7) % N, r)
+    return 3 * len(rumors)
 
 
 class _Recorder:

@@ -1,8 +1,13 @@
 """GPU: the fanout and rumor-count classes of the dense emit that no other test runs, against the
-C oracle bit for bit.  make_bin_geom halves the sender tile until ts * k <= 16384: k = 4, 7, 8, 16,
-17, 32, 33 give ts = 4096, 2048, 2048, 1024, 512, 512, 256, with exactly full regions (ts * k ==
-16384) at k = 4, 8, 16, 32; the binned sparse scan takes k <= 4; loss draws with j >> 2 above 1
-start at k = 9.  41037 nodes are three destination tiles with a ragged last one."""
+C oracle bit for bit.  make_bin_geom halves the sender tile until ts * k <= 16384:
+
+    k    4     7     8     16    17   32   33   34   63   64
+    ts   4096  2048  2048  1024  512  512  256  256  256  256
+
+with exactly full regions (ts * k == 16384) at k = 4, 8, 16, 32 and at the maximum fanout, 64; from
+k = 33 up the tile stays at 256 senders.  The binned sparse scan takes k <= 4; loss draws with
+j >> 2 above 1 start at k = 9 and reach Philox block 15 at k = 64.  41037 nodes are three
+destination tiles with a ragged last one."""
 import functools
 import os
 
@@ -53,9 +58,11 @@ def _compare(N_, R, mode, k, path, loss=0, parts=0, work="random", rounds=MAX_RO
 
 
 # the issue's rotation push / pull / pushpull over k = 4 .. 33 gives pull no power-of-two fanout and
-# push-pull none that is not; the last two cases add them
+# push-pull none that is not; the next two cases add them; the last five are the classes above 33, up
+# to the maximum fanout in every mode
 SWEEP = [("push", 4), ("pull", 7), ("pushpull", 8), ("push", 16), ("pull", 17), ("pushpull", 32), ("push", 33),
-         ("pull", 16), ("pushpull", 7)]
+         ("pull", 16), ("pushpull", 7),
+         ("pull", 34), ("pushpull", 63), ("push", 64), ("pull", 64), ("pushpull", 64)]
 
 
 @pytest.mark.parametrize("path", PATHS)
@@ -71,9 +78,11 @@ def test_fanout4_one_rumor(path):
 
 
 @pytest.mark.parametrize("path", list(st.FAULT_PATHS))
-@pytest.mark.parametrize("mode,k,loss,parts", [("push", 4, 0.2, 5), ("pushpull", 8, 0.3, 0), ("pull", 17, 0.25, 2)])
+@pytest.mark.parametrize("mode,k,loss,parts", [("push", 4, 0.2, 5), ("pushpull", 8, 0.3, 0), ("pull", 17, 0.25, 2),
+                                               ("push", 64, 0.9, 0)])
 def test_fanout_faults(mode, k, loss, parts, path):
-    """Loss draws of edge j come from Philox block j >> 2: k = 8 reaches block 1, k = 17 block 4.
+    """Loss draws of edge j come from Philox block j >> 2: k = 8 reaches block 1, k = 17 block 4,
+    k = 64 block 15 (nine edges in ten lost, so that the run still takes several rounds).
     With partitions no rumor leaves its block, so those runs go the whole 64 rounds unconverged."""
     want, _ = _compare(N, 64, mode, k, st.FAULT_PATHS[path], loss=loss_threshold(loss), parts=parts, converges=None)
     assert want.converged == (parts == 0)
