@@ -32,6 +32,14 @@ struct AexArgs {
   Faults fa;                // lost edges (global N, stall null): the same on every rank
 };
 
+// The same arguments with the rows of the topology behind them (DESIGN.md §2.12,
+// GOSSIP_FLAG_AE_TOPO_PEERS): the CSR over all N nodes (global ids, rows as sorted sets), which
+// only the TOPO instantiations of the list kernel read.
+struct AexTArgs : AexArgs {
+  const uint32_t* orow;  // [N + 1]
+  const uint32_t* ocol;  // [orow[N]] every entry < N
+};
+
 // entries of the per-block tables (bcnt, boff) for nown own nodes and G shards
 size_t aex_block_table_words(uint64_t nown, uint32_t G);
 
@@ -44,6 +52,8 @@ hipError_t launch_aex_churn(const AexArgs& a, hipStream_t st);
 // the own nodes' exchanges of round t (after the all-gather): messages counted, those with a
 // stale end listed (count pass, scan, fill pass)
 hipError_t launch_aex_requests(const AexArgs& a, hipStream_t st);
+// the same with exchange j of node n aimed at row_n[floor(x_j * deg(n) / 2^32)]
+hipError_t launch_aex_requests_topo(const AexTArgs& a, hipStream_t st);
 // requests received (m items): max-merge into Vn, responses V_t[p] in the received order
 hipError_t launch_aex_serve(const AexArgs& a, const uint32_t* in, uint64_t m, uint32_t* resp, hipStream_t st);
 // the responses to the own requests (in request order), the own-own exchanges, then the

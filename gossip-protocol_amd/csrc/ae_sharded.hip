@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "philox.h"
+#include "topo_peers.h"
 #include "wave.h"
 
 namespace gossip {
@@ -67,8 +68,12 @@ __device__ __forceinline__ void block_range(const AexArgs& a, uint64_t* i0, uint
 // FAULTS: a lost edge (philox.h edge_lost) is no message and lists nothing.  The
 // count pass decides; the k <= 8 fill pass follows its verdicts, the k > 8 one redraws the loss
 // words and applies the same test, so both passes count the same items per owner.
-template <bool FILL, bool FAULTS>
-__global__ __launch_bounds__(kAxBlock) void aex_list_kernel(AexArgs a, uint32_t* bcnt, const uint64_t* boff) {
+// TOPO: the peers come from the node's row of the global CSR (AexTArgs), by the
+// same word and the same index in both passes; a node with an empty row lists nothing.  An own-own
+// exchange (n, n) of a self-loop is listed like any other and moves nothing in the merge.
+template <bool FILL, bool FAULTS, bool TOPO>
+__global__ __launch_bounds__(kAxBlock) void aex_list_kernel(
+    typename std::conditional<TOPO, AexTArgs, AexArgs>::type a, uint32_t* bcnt, const uint64_t* boff) {
   constexpr uint32_t kStage = kAxBlock * 8;  // items one pass of the block lists at most (k <= 8)
   __shared__ uint32_t c[kAxMaxG + 1];
   __shared__ uint64_t red[kAxBlock / 64];
@@ -108,9 +113,22 @@ __global__ __launch_bounds__(kAxBlock) void aex_list_kernel(AexArgs a, uint32_t*
       const bool decide = !(FILL && verdicts);  // this pass tests the edges itself
       Reach rc{0u, 0xFFFFFFFFu};
       if (FAULTS && decide) rc = reach_of((uint32_t)n, a.fa);
-      for (uint32_t j = 0; j < a.k; ++j) {
+      uint32_t rb = 0, rd = 0;  // the node's row: first entry, entries
+      if constexpr (TOPO) {
+        rb = a.orow[n];
+        rd = a.orow[n + 1] - rb;
+      }
+      const uint32_t kj = TOPO && rd == 0 ? 0u : a.k;  // an empty row initiates nothing
+      for (uint32_t j = 0; j < kj; ++j) {
         if ((j & 3u) == 0) x = philox4x32_10(u32x4{(uint32_t)n, a.t, 0u, j >> 2}, a.key0, a.key1);
-        const uint32_t p = peer_from_word(lane_of(x, j & 3u), nm1, (uint32_t)n);
+        uint32_t p;
+        if constexpr (TOPO) {
+          // (a fill pass that follows verdicts reads only the entries of the exchanges it lists)
+          if (FILL && verdicts && !((vb >> j) & 1u)) continue;
+          p = a.ocol[rb + topo_index_from_word(lane_of(x, j & 3u), rd)];
+        } else {
+          p = peer_from_word(lane_of(x, j & 3u), nm1, (uint32_t)n);
+        }
         if (FAULTS && decide && (j & 3u) == 0 && a.fa.loss) lw = loss_draws((uint32_t)n, a.t, j >> 2, a.key0, a.key1);
         if (FILL && verdicts) {
           if (!((vb >> j) & 1u)) continue;
@@ -521,20 +539,27 @@ hipError_t launch_aex_churn(const AexArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_aex_requests(const AexArgs& a, hipStream_t st) {
+namespace {
+// count pass, totals and offsets, fill pass; A = AexTArgs: the peers through the rows
+template <bool TOPO, class A>
+hipError_t requests_l(const A& a, hipStream_t st) {
   if (a.G > kAxMaxG) return hipErrorInvalidValue;
   const uint32_t nb = list_blocks(a.nown);
   uint32_t* bcnt = a.bcnt;
   uint64_t* boff = a.boff;
   const bool faults = a.fa.any();
-  if (faults) aex_list_kernel<false, true><<<nb, kAxBlock, 0, st>>>(a, bcnt, nullptr);
-  else aex_list_kernel<false, false><<<nb, kAxBlock, 0, st>>>(a, bcnt, nullptr);
+  if (faults) aex_list_kernel<false, true, TOPO><<<nb, kAxBlock, 0, st>>>(a, bcnt, nullptr);
+  else aex_list_kernel<false, false, TOPO><<<nb, kAxBlock, 0, st>>>(a, bcnt, nullptr);
   aex_total_kernel<<<a.G + 1, kAxBlock, 0, st>>>(a, bcnt, nb);
   aex_scan_kernel<<<a.G + 1, kAxBlock, 0, st>>>(a, bcnt, boff, nb);
-  if (faults) aex_list_kernel<true, true><<<nb, kAxBlock, 0, st>>>(a, bcnt, boff);
-  else aex_list_kernel<true, false><<<nb, kAxBlock, 0, st>>>(a, bcnt, boff);
+  if (faults) aex_list_kernel<true, true, TOPO><<<nb, kAxBlock, 0, st>>>(a, bcnt, boff);
+  else aex_list_kernel<true, false, TOPO><<<nb, kAxBlock, 0, st>>>(a, bcnt, boff);
   return hipGetLastError();
 }
+}  // namespace
+
+hipError_t launch_aex_requests(const AexArgs& a, hipStream_t st) { return requests_l<false>(a, st); }
+hipError_t launch_aex_requests_topo(const AexTArgs& a, hipStream_t st) { return requests_l<true>(a, st); }
 
 hipError_t launch_aex_serve(const AexArgs& a, const uint32_t* in, uint64_t m, uint32_t* resp, hipStream_t st) {
   if (m == 0) return hipSuccess;

@@ -69,6 +69,22 @@ struct AeFArgs : AeArgs {
   Faults fa;
 };
 
+// Anti-entropy over the topology (GOSSIP_FLAG_AE_TOPO_PEERS): exchange j of node n
+// goes to row_n[floor(x_j * deg(n) / 2^32)] instead of a node drawn from all N; an empty row
+// initiates nothing.  The rows (sorted sets, CSR over all N nodes) reach only the TOPO
+// instantiations of the kernels that draw a peer, through these derived structs, so every other
+// engine keeps the kernels and the argument layouts above.
+struct AeRows {
+  const uint32_t* orow;  // [N + 1]
+  const uint32_t* ocol;  // [orow[N]] every entry < N
+};
+struct AeTArgs : AeArgs {
+  AeRows tp;
+};
+struct AeTFArgs : AeFArgs {
+  AeRows tp;
+};
+
 // binned sparse-scan geometry for N nodes, k exchanges per node
 struct AeBinGeom {
   uint32_t tl, nt, rs, nreg;
@@ -90,6 +106,10 @@ hipError_t launch_ae_stats(const AeArgs& a, const uint32_t* V, uint64_t* ab, boo
 // sparse round (after the churn): scan (edges touching a stale node), gather, apply in
 // place, fix-up (stale bits, hash delta into partial[3]), then stats from the bitmaps
 hipError_t launch_ae_sparse(const AeFArgs& a, hipStream_t st);
+// the same two rounds with the peers drawn from the rows: pull + push, and the
+// direct scan + gather + apply + fix-up; churn before and stats after as for the calls above
+hipError_t launch_ae_round_topo(const AeTFArgs& a, hipStream_t st);
+hipError_t launch_ae_sparse_topo(const AeTFArgs& a, hipStream_t st);
 // the same round with the binned scan (a.brec set, a.nseg == a.bnt); its first
 // pass also does the churn (no launch_ae_churn before it)
 hipError_t launch_ae_sparse_binned(const AeFArgs& a, hipStream_t st);

@@ -7,7 +7,9 @@
 // reference's only failure handling is retry-until-acked (main.go:77-87);
 // churn here is the build-defined fault model of SURVEY.md §5.  Edge loss and
 // partitions drop single exchanges on top of it: AeEdges below,
-// in the FAULTS instantiations of the kernels that decide an exchange from a draw.
+// in the FAULTS instantiations of the kernels that decide an exchange from a draw.  Over the
+// topology the peer comes from the node's own row: AePeers below, in the
+// TOPO instantiations of the same kernels (the pull and push passes and the direct scan).
 //
 // Every kernel walks 64-node chunks, one chunk per wave.  The node phase runs
 // one lane per node (Philox peer draw, the peer's alive bit from the churn
@@ -34,6 +36,7 @@
 #include <type_traits>
 
 #include "philox.h"
+#include "topo_peers.h"
 #include "wave.h"
 
 namespace gossip {
@@ -141,8 +144,10 @@ __device__ __forceinline__ uint32_t peer_j(const AeArgs& a, uint32_t n, uint32_t
 // lost(j, p) is asked for j = 0, 1, ... in order (every j, as peer_j), so every kernel that decides
 // an exchange from a peer draw makes the same decision.  FAULTS = false: no code at all.
 // A FAULTS kernel takes the round's arguments with the faults (AeFArgs), the others AeArgs alone.
-template <bool FAULTS>
-using AeK = typename std::conditional<FAULTS, AeFArgs, AeArgs>::type;
+// A TOPO kernel takes the same arguments with the rows behind them (AeTArgs, AeTFArgs).
+template <bool FAULTS, bool TOPO = false>
+using AeK = typename std::conditional<TOPO, typename std::conditional<FAULTS, AeTFArgs, AeTArgs>::type,
+                                      typename std::conditional<FAULTS, AeFArgs, AeArgs>::type>::type;
 
 template <bool FAULTS>
 struct AeEdges {
@@ -158,6 +163,58 @@ template <>
 struct AeEdges<false> {  // no faults: no state, no code
   __device__ __forceinline__ AeEdges(const AeArgs&, uint32_t) {}
   __device__ __forceinline__ bool lost(const AeArgs&, uint32_t, uint32_t, uint32_t) { return false; }
+};
+
+// The peers of node n's exchanges in round a.t.  peer(j) is asked for j = 0, 1, ... in order (the
+// Philox block of j .. j + 3 is drawn at j % 4 == 0); peer_if(j, want) likewise, and resolves the
+// peer only where want (or where the block is drawn: the uniform draw is one multiply more).
+// TOPO = false: peer_j, uniform over the other N - 1 nodes, and no node is without peers.
+template <bool TOPO>
+struct AePeers {
+  u32x4 x{0u, 0u, 0u, 0u};
+  __device__ __forceinline__ AePeers(const AeArgs&, uint32_t, bool) {}
+  __device__ __forceinline__ bool none() const { return false; }
+  __device__ __forceinline__ uint32_t peer(const AeArgs& a, uint32_t n, uint32_t j) { return peer_j(a, n, j, x); }
+  __device__ __forceinline__ uint32_t peer_if(const AeArgs& a, uint32_t n, uint32_t j, bool want) {
+    return ((j & 3u) == 0 || want) ? peer_j(a, n, j, x) : 0u;
+  }
+};
+// TOPO: p_j = row_n[floor(x_j * d / 2^32)], topo_index_from_word as §2.10.  The
+// two orow reads are coalesced over the 64 nodes of a chunk (in = n < N: a lane past N reads
+// nothing and has d = 0).  A node with d == 0 has no peers (none()): its lane asks for none and
+// still takes part in every ballot and shuffle of its wave.  peer() issues the index loads of a
+// whole Philox block (up to four exchanges, all of them when k <= 4) before the first is
+// consumed, so the row gathers of exchange j do not wait between two dependent loads each.
+template <>
+struct AePeers<true> {
+  uint32_t b = 0, d = 0;
+  u32x4 x{0u, 0u, 0u, 0u}, pq{0u, 0u, 0u, 0u};
+  template <class A>
+  __device__ __forceinline__ AePeers(const A& a, uint32_t n, bool in) {
+    if (in) {
+      b = a.tp.orow[n];
+      d = a.tp.orow[n + 1] - b;
+    }
+  }
+  __device__ __forceinline__ bool none() const { return d == 0; }
+  template <class A>
+  __device__ __forceinline__ uint32_t peer(const A& a, uint32_t n, uint32_t j) {  // d > 0
+    if ((j & 3u) == 0) {
+      x = philox4x32_10(u32x4{n, a.t, 0u, j >> 2}, a.key0, a.key1);
+      const uint32_t* __restrict__ row = a.tp.ocol + b;
+      const uint32_t m = a.k - j;  // exchanges left, this one included
+      pq.x = row[topo_index_from_word(x.x, d)];
+      pq.y = m > 1 ? row[topo_index_from_word(x.y, d)] : 0u;
+      pq.z = m > 2 ? row[topo_index_from_word(x.z, d)] : 0u;
+      pq.w = m > 3 ? row[topo_index_from_word(x.w, d)] : 0u;
+    }
+    return lane_of(pq, j & 3u);
+  }
+  template <class A>
+  __device__ __forceinline__ uint32_t peer_if(const A& a, uint32_t n, uint32_t j, bool want) {  // want: d > 0
+    if ((j & 3u) == 0) x = philox4x32_10(u32x4{n, a.t, 0u, j >> 2}, a.key0, a.key1);
+    return want ? a.tp.ocol[b + topo_index_from_word(lane_of(x, j & 3u), d)] : 0u;
+  }
 };
 
 __global__ __launch_bounds__(kAeBlock) void ae_fill_alive_kernel(uint64_t* ab, uint64_t N) {
@@ -201,8 +258,8 @@ struct MaskOf {  // one bit per lane of a node's group
 // pull pass: Vn[n] = max(V[n], V[p_j] for every exchange j of n) — plain stores of
 // every row — and, per exchange, the mask of components where V[n] > V[p_j]: the
 // push pass then needs neither the peer's row nor its alive bit
-template <uint32_t L, bool FAULTS>
-__global__ __launch_bounds__(kAeBlock) void ae_pull_kernel(AeK<FAULTS> a) {
+template <uint32_t L, bool FAULTS, bool TOPO>
+__global__ __launch_bounds__(kAeBlock) void ae_pull_kernel(AeK<FAULTS, TOPO> a) {
   using MT = typename MaskOf<L>::T;
   constexpr uint32_t per = 64 / L;
   constexpr uint64_t gmask = L >= 64 ? ~0ull : ((1ull << L) - 1ull);
@@ -223,13 +280,13 @@ __global__ __launch_bounds__(kAeBlock) void ae_pull_kernel(AeK<FAULTS> a) {
       own[i] = (node < a.N && c < a.K) ? V[node * a.K + c] : 0u;
       acc[i] = own[i];
     }
-    u32x4 x{0, 0, 0, 0};
+    AePeers<TOPO> pe(a, n, ch * 64 + lane < a.N);
     AeEdges<FAULTS> fe(a, n);
     for (uint32_t j = 0; j < a.k; ++j) {
       uint32_t p = 0;
       bool ex = false;
-      if (aln) {
-        p = peer_j(a, n, j, x);
+      if (aln && !pe.none()) {
+        p = pe.peer(a, n, j);
         const bool lost = fe.lost(a, n, j, p);  // (every j: the loss words are drawn at j % 4 == 0)
         ex = alive_bit(a.abn, p) && !lost;
       }
@@ -266,8 +323,8 @@ __global__ __launch_bounds__(kAeBlock) void ae_pull_kernel(AeK<FAULTS> a) {
 }
 
 // push pass: atomicMax(Vn[p_j][c], V[n][c]) for the components c of the pull pass's mask
-template <uint32_t L>
-__global__ __launch_bounds__(kAeBlock) void ae_push_kernel(AeArgs a) {
+template <uint32_t L, bool TOPO>
+__global__ __launch_bounds__(kAeBlock) void ae_push_kernel(AeK<false, TOPO> a) {
   using MT = typename MaskOf<L>::T;
   constexpr uint32_t per = 64 / L;
   const uint32_t lane = threadIdx.x & 63, sub = lane / L, c = lane % L;
@@ -278,12 +335,12 @@ __global__ __launch_bounds__(kAeBlock) void ae_push_kernel(AeArgs a) {
   for (uint64_t ch = wave_id(); ch < chunks; ch += wave_count()) {
     const uint64_t nl = ch * 64 + lane;
     const uint32_t n = (uint32_t)nl;
-    u32x4 x{0, 0, 0, 0};
+    AePeers<TOPO> pe(a, n, nl < a.N);
     for (uint32_t j = 0; j < a.k; ++j) {
       const uint64_t mw = nl < a.N ? (uint64_t)pm[nl * a.k + j] : 0ull;
       // Philox words for j..j+3 are drawn at j % 4 == 0 whatever the masks say
-      uint32_t p = 0;
-      if ((j & 3u) == 0 || mw) p = peer_j(a, n, j, x);
+      // (a mask bit means the pull pass saw this exchange: the node has a row to draw from)
+      const uint32_t p = pe.peer_if(a, n, j, mw != 0);
       if (!__ballot(mw != 0)) continue;
       // every load in flight first: the pushed component and the peer's current
       // S_{t+1} value (its pull pass is done; values only grow, so a component
@@ -376,8 +433,8 @@ __global__ __launch_bounds__(kAeBlock) void ae_stats_kernel(AeArgs a, const uint
 // --------------------------------------------------------------- sparse round
 // Scan: block b owns chunks [b*spc, (b+1)*spc) and lists, into its own segment,
 // the exchanges with a stale end (LDS slot counter); past segcap only counted.
-template <bool FAULTS>
-__global__ __launch_bounds__(kAeBlock) void ae_sparse_scan_kernel(AeK<FAULTS> a) {
+template <bool FAULTS, bool TOPO>
+__global__ __launch_bounds__(kAeBlock) void ae_sparse_scan_kernel(AeK<FAULTS, TOPO> a) {
   __shared__ uint64_t red[kAeWaves];
   __shared__ uint32_t scnt;
   const uint32_t lane = threadIdx.x & 63;
@@ -393,13 +450,13 @@ __global__ __launch_bounds__(kAeBlock) void ae_sparse_scan_kernel(AeK<FAULTS> a)
     const uint32_t n = (uint32_t)(ch * 64 + lane);
     const bool aln = (a.abn[2 * ch] >> lane) & 1ull;
     const bool own_stale = (a.abn[2 * ch + 1] >> lane) & 1ull;
-    u32x4 x{0, 0, 0, 0};
+    AePeers<TOPO> pe(a, n, ch * 64 + lane < a.N);
     AeEdges<FAULTS> fe(a, n);
     for (uint32_t j = 0; j < a.k; ++j) {
       uint32_t p = 0;
       bool ex = false, pst = false;
-      if (aln) {
-        p = peer_j(a, n, j, x);
+      if (aln && !pe.none()) {
+        p = pe.peer(a, n, j);
         alive_stale(a.abn, p, &ex, &pst);
         if (fe.lost(a, n, j, p)) ex = false;
       }
@@ -1362,19 +1419,41 @@ hipError_t launch_ae_churn(const AeArgs& a, hipStream_t st) {
 }
 
 namespace {
-template <bool FAULTS>
-void ae_pull_l(const AeFArgs& f, hipStream_t st) {
-  const AeK<FAULTS>& a = f;
+// a: the arguments of the instantiation (AeK<FAULTS, TOPO>)
+template <bool FAULTS, bool TOPO = false>
+void ae_pull_l(const AeK<FAULTS, TOPO>& a, hipStream_t st) {
   const uint32_t g = chunk_grid(a.N);
   switch (a.L) {
-    case 1: ae_pull_kernel<1, FAULTS><<<g, kAeBlock, 0, st>>>(a); break;
-    case 2: ae_pull_kernel<2, FAULTS><<<g, kAeBlock, 0, st>>>(a); break;
-    case 4: ae_pull_kernel<4, FAULTS><<<g, kAeBlock, 0, st>>>(a); break;
-    case 8: ae_pull_kernel<8, FAULTS><<<g, kAeBlock, 0, st>>>(a); break;
-    case 16: ae_pull_kernel<16, FAULTS><<<g, kAeBlock, 0, st>>>(a); break;
-    case 32: ae_pull_kernel<32, FAULTS><<<g, kAeBlock, 0, st>>>(a); break;
-    default: ae_pull_kernel<64, FAULTS><<<g, kAeBlock, 0, st>>>(a); break;
+    case 1: ae_pull_kernel<1, FAULTS, TOPO><<<g, kAeBlock, 0, st>>>(a); break;
+    case 2: ae_pull_kernel<2, FAULTS, TOPO><<<g, kAeBlock, 0, st>>>(a); break;
+    case 4: ae_pull_kernel<4, FAULTS, TOPO><<<g, kAeBlock, 0, st>>>(a); break;
+    case 8: ae_pull_kernel<8, FAULTS, TOPO><<<g, kAeBlock, 0, st>>>(a); break;
+    case 16: ae_pull_kernel<16, FAULTS, TOPO><<<g, kAeBlock, 0, st>>>(a); break;
+    case 32: ae_pull_kernel<32, FAULTS, TOPO><<<g, kAeBlock, 0, st>>>(a); break;
+    default: ae_pull_kernel<64, FAULTS, TOPO><<<g, kAeBlock, 0, st>>>(a); break;
   }
+}
+
+template <bool TOPO>
+void ae_push_l(const AeK<false, TOPO>& a, hipStream_t st) {
+  const uint32_t g = chunk_grid(a.N);
+  switch (a.L) {
+    case 1: ae_push_kernel<1, TOPO><<<g, kAeBlock, 0, st>>>(a); break;
+    case 2: ae_push_kernel<2, TOPO><<<g, kAeBlock, 0, st>>>(a); break;
+    case 4: ae_push_kernel<4, TOPO><<<g, kAeBlock, 0, st>>>(a); break;
+    case 8: ae_push_kernel<8, TOPO><<<g, kAeBlock, 0, st>>>(a); break;
+    case 16: ae_push_kernel<16, TOPO><<<g, kAeBlock, 0, st>>>(a); break;
+    case 32: ae_push_kernel<32, TOPO><<<g, kAeBlock, 0, st>>>(a); break;
+    default: ae_push_kernel<64, TOPO><<<g, kAeBlock, 0, st>>>(a); break;
+  }
+}
+
+// the round's arguments without the faults, the rows kept
+AeTArgs ae_rows_only(const AeTFArgs& f) {
+  AeTArgs t{};
+  static_cast<AeArgs&>(t) = f;
+  t.tp = f.tp;
+  return t;
 }
 
 // the emit of a binned round: NT tile counters, grid eg; k == 1 with full regions keeps the peers
@@ -1416,7 +1495,15 @@ void ae_dense_apply(const AeFArgs& f, hipStream_t st) {
 hipError_t launch_ae_round(const AeFArgs& a, hipStream_t st) {
   if (a.fa.any()) ae_pull_l<true>(a, st);
   else ae_pull_l<false>(a, st);
-  AE_LAUNCH_L(ae_push_kernel, a.L, chunk_grid(a.N), st, a);
+  ae_push_l<false>(a, st);
+  return hipGetLastError();
+}
+
+hipError_t launch_ae_round_topo(const AeTFArgs& a, hipStream_t st) {
+  const AeTArgs t = ae_rows_only(a);
+  if (a.fa.any()) ae_pull_l<true, true>(a, st);
+  else ae_pull_l<false, true>(t, st);
+  ae_push_l<true>(t, st);
   return hipGetLastError();
 }
 
@@ -1426,8 +1513,19 @@ hipError_t launch_ae_stats(const AeArgs& a, const uint32_t* V, uint64_t* ab, boo
 }
 
 hipError_t launch_ae_sparse(const AeFArgs& a, hipStream_t st) {
-  if (a.fa.any()) ae_sparse_scan_kernel<true><<<a.nseg, kAeBlock, 0, st>>>(a);
-  else ae_sparse_scan_kernel<false><<<a.nseg, kAeBlock, 0, st>>>(static_cast<const AeArgs&>(a));
+  if (a.fa.any()) ae_sparse_scan_kernel<true, false><<<a.nseg, kAeBlock, 0, st>>>(a);
+  else ae_sparse_scan_kernel<false, false><<<a.nseg, kAeBlock, 0, st>>>(static_cast<const AeArgs&>(a));
+  AE_LAUNCH_L(ae_sparse_gather_kernel, a.L, a.nseg * a.spb, st, a);
+  AE_LAUNCH_L(ae_sparse_apply_kernel, a.L, a.nseg * a.spb, st, a);
+  AE_LAUNCH_L(ae_sparse_fix_kernel, a.L, a.nseg * a.spb, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_ae_sparse_topo(const AeTFArgs& a, hipStream_t st) {
+  if (a.fa.any()) ae_sparse_scan_kernel<true, true><<<a.nseg, kAeBlock, 0, st>>>(a);
+  else ae_sparse_scan_kernel<false, true><<<a.nseg, kAeBlock, 0, st>>>(ae_rows_only(a));
+  // the edge list is all the rest reads: an edge (n, n) snapshots one row twice, moves nothing
+  // and is claimed once; a pair listed twice merges the same two snapshots twice
   AE_LAUNCH_L(ae_sparse_gather_kernel, a.L, a.nseg * a.spb, st, a);
   AE_LAUNCH_L(ae_sparse_apply_kernel, a.L, a.nseg * a.spb, st, a);
   AE_LAUNCH_L(ae_sparse_fix_kernel, a.L, a.nseg * a.spb, st, a);

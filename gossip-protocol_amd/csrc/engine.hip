@@ -99,6 +99,7 @@ struct gossip_engine {
   DevBuf<uint32_t> orow, ocol, irow, icol;
   bool has_topo = false;
   bool topo_peers = false;  // GOSSIP_FLAG_TOPO_PEERS: random modes draw their peers from the rows
+  bool ae_topo = false;     // GOSSIP_FLAG_AE_TOPO_PEERS: ANTIENTROPY exchanges go to peers from the rows (§2.12)
   // stall mode, random modes: streak per node, all N nodes on every shard
   DevBuf<uint8_t> stall_d;
   // FLOOD with faults, one shard: per out-edge pending values and first senders
@@ -295,6 +296,7 @@ int need_topo(gossip_engine* e) {
   if (e->has_topo) return GOSSIP_OK;
   if (e->mode == GOSSIP_MODE_FLOOD) return e->fail(GOSSIP_ESTATE, "FLOOD needs a topology");
   if (e->topo_peers) return e->fail(GOSSIP_ESTATE, "GOSSIP_FLAG_TOPO_PEERS needs a topology");
+  if (e->ae_topo) return e->fail(GOSSIP_ESTATE, "GOSSIP_FLAG_AE_TOPO_PEERS needs a topology");
   return GOSSIP_OK;
 }
 
@@ -451,6 +453,14 @@ AeFArgs make_ae_args(gossip_engine* e) {
   a.spb = std::max<uint32_t>(1, 4096 / e->ae_nseg);  // ~4096 blocks over the edge list
   a.epoch = e->ae_epoch;
   a.fa = Faults{e->fa.loss, e->fa.parts, e->N};  // (no stall model: DESIGN.md §2.11)
+  return a;
+}
+
+// the round's arguments with the rows behind them (GOSSIP_FLAG_AE_TOPO_PEERS)
+AeTFArgs make_ae_topo_args(gossip_engine* e) {
+  AeTFArgs a{};
+  static_cast<AeFArgs&>(a) = make_ae_args(e);
+  a.tp = AeRows{e->orow, e->ocol};
   return a;
 }
 
@@ -930,7 +940,8 @@ int ae_round(gossip_engine* e) {
       a.zero = nullptr;
     } else {
       HIP_OK(e, launch_ae_churn(a, e->stream));
-      HIP_OK(e, launch_ae_sparse(a, e->stream));
+      if (e->ae_topo) HIP_OK(e, launch_ae_sparse_topo(make_ae_topo_args(e), e->stream));
+      else HIP_OK(e, launch_ae_sparse(a, e->stream));
     }
     if ((rc = timer_end(e, 2))) return rc;
     if ((rc = timer_begin(e, 1))) return rc;
@@ -972,7 +983,8 @@ int ae_round(gossip_engine* e) {
     if (!binned) {
       if ((rc = timer_begin(e, 0))) return rc;
       HIP_OK(e, launch_ae_churn(a, e->stream));
-      HIP_OK(e, launch_ae_round(a, e->stream));
+      if (e->ae_topo) HIP_OK(e, launch_ae_round_topo(make_ae_topo_args(e), e->stream));
+      else HIP_OK(e, launch_ae_round(a, e->stream));
       if ((rc = timer_end(e, 0))) return rc;
       if ((rc = timer_begin(e, 1))) return rc;
       HIP_OK(e, launch_ae_stats(a, e->Vn, e->alive_n, true, e->stream));
@@ -1338,6 +1350,11 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
     g_create_error = "GOSSIP_FLAG_TOPO_PEERS applies to PUSH, PULL and PUSHPULL (FLOOD sends to the whole row)";
     return GOSSIP_EINVAL;
   }
+  if ((cfg->flags & GOSSIP_FLAG_AE_TOPO_PEERS) && cfg->mode != GOSSIP_MODE_ANTIENTROPY) {
+    g_create_error = "GOSSIP_FLAG_AE_TOPO_PEERS applies to ANTIENTROPY (the random modes take GOSSIP_FLAG_TOPO_PEERS, "
+                     "FLOOD sends to the whole row)";
+    return GOSSIP_EINVAL;
+  }
   const uint32_t G = cfg->shard_count ? cfg->shard_count : 1;
   if (cfg->shard_rank >= G) {
     g_create_error = "shard_rank >= shard_count";
@@ -1400,6 +1417,7 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
   e->timing = (cfg->flags & GOSSIP_FLAG_TIMING) != 0;
   e->flood_edges = e->mode == GOSSIP_MODE_FLOOD && faulty;
   e->topo_peers = (cfg->flags & GOSSIP_FLAG_TOPO_PEERS) != 0;
+  e->ae_topo = (cfg->flags & GOSSIP_FLAG_AE_TOPO_PEERS) != 0;
   // such engines run the direct kernels: never binned, no sparse-sharded or exchange state
   const uint32_t direct_flags = GOSSIP_FLAG_DIRECT | GOSSIP_FLAG_TOPO_PEERS;
   e->fw.D = cfg->stall_rounds;
@@ -1471,9 +1489,11 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
       return bail(GOSSIP_ENOMEM);
     if (launch_ae_fill_alive(e->alive, e->N, nullptr) != hipSuccess) return bail(GOSSIP_EHIP);
     e->ae_bg = ae_bin_geom(e->N, e->k);
-    e->ae_bin = !(cfg->flags & GOSSIP_FLAG_AE_DIRECT_SCAN) && e->k <= 16 && ae_bin_fits(e->ae_bg);  // else the direct scan
+    // (over the topology, §2.12: the kernels that decide an exchange where it is drawn, one round at a time)
+    e->ae_bin = !(cfg->flags & GOSSIP_FLAG_AE_DIRECT_SCAN) && !e->ae_topo && e->k <= 16 &&
+                ae_bin_fits(e->ae_bg);  // else the direct scan
     e->ae_dg = ae_dense_geom(e->N, e->k);
-    e->ae_dbin = ae_dense_fits(e->ae_dg, e->N, e->k, e->R);  // else pull + atomicMax push + stats
+    e->ae_dbin = !e->ae_topo && ae_dense_fits(e->ae_dg, e->N, e->k, e->R);  // else pull + atomicMax push + stats
     if (e->ae_dbin && !alloc(e->ae_dboff, (size_t)e->ae_dg.nreg * (e->ae_dg.nt + 1))) return bail(GOSSIP_ENOMEM);
     if (e->ae_bin || e->ae_dbin) {
       const size_t recs = (size_t)e->ae_bg.nreg * ((size_t)e->k << e->ae_bg.rs);
@@ -2015,6 +2035,8 @@ int gossip_local_totals(gossip_engine_t* e, uint64_t* partial) {
 int gossip_sharded_plan(gossip_engine_t* e, const uint64_t* total, int32_t* kind) {
   if (!e || !kind) return GOSSIP_EINVAL;
   e->sx_planned = e->xd_planned = e->cc_planned = e->rep_planned = false;
+  // (§2.12: every rank fails here, before the round's first collective, so none waits in one)
+  if (e->ae_topo && !e->has_topo) return e->fail(GOSSIP_ESTATE, "GOSSIP_FLAG_AE_TOPO_PEERS needs a topology");
   if (e->aex) {  // 2: an anti-entropy exchange round; -2: the global max vector is needed first
     *kind = e->aex_target_ok ? 2 : -2;
     return GOSSIP_OK;
@@ -2446,13 +2468,22 @@ int gossip_ae_requests(gossip_engine_t* e, void** send, uint64_t* send_counts) {
   if (int rc = aex_check(e)) return rc;
   if (!e->aex_target_ok) return e->fail(GOSSIP_ESTATE, "the global max vector is stale: gossip_ae_set_target first");
   if (e->aex_churned != e->t) return e->fail(GOSSIP_ESTATE, "gossip_exchange_buffers (and its all-gather) first");
+  if (int rc = need_topo(e)) return rc;
   const AexArgs a = make_aex_args(e);
   HIP_OK(e, hipMemsetAsync(e->partial_d, 0, part_len(e) * 8, e->stream));
   // S_{t+1} starts as S_t (max only grows): the rows the last round raised, or every row
   HIP_OK(e, launch_aex_seed_next(a, e->aex_dirty, e->aex_patch_ok, e->stream));
   e->aex_patch_ok = e->aex_round_done = e->aex_track = false;
   if (int rc = timer_begin(e, 0)) return rc;
-  HIP_OK(e, launch_aex_requests(a, e->stream));
+  if (e->ae_topo) {  // the peers through the rows of the global CSR
+    AexTArgs ta{};
+    static_cast<AexArgs&>(ta) = a;
+    ta.orow = e->orow;
+    ta.ocol = e->ocol;
+    HIP_OK(e, launch_aex_requests_topo(ta, e->stream));
+  } else {
+    HIP_OK(e, launch_aex_requests(a, e->stream));
+  }
   HIP_OK(e, hipMemcpyAsync(e->aex_cnt_h, e->aex_cnt, (e->G + 1) * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(e, hipStreamSynchronize(e->stream));
   uint64_t nreq = 0;

@@ -17,6 +17,7 @@ FLAG_DENSE = 1 << 3
 FLAG_SHARD_DIRECT = 1 << 4
 FLAG_AE_DIRECT_SCAN = 1 << 5
 FLAG_TOPO_PEERS = 1 << 6  # random modes: peers drawn from the node's topology row
+FLAG_AE_TOPO_PEERS = 1 << 7  # ANTIENTROPY: exchange peers drawn from the node's topology row
 
 ABI_VERSION = 10  # include/gossip.h GOSSIP_ABI_VERSION (v10: gossip_round_wall)
 

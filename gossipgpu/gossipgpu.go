@@ -56,7 +56,8 @@ const (
 )
 
 // Flags select optional outputs and A/B round paths (results never change), and with
-// FlagTopoPeers the peer source of the random modes (results do change: include/gossip.h).
+// FlagTopoPeers / FlagAeTopoPeers the peer source of the random modes / of AntiEntropy (results
+// do change: include/gossip.h).
 type Flags uint32
 
 const (
@@ -69,6 +70,9 @@ const (
 	// FlagTopoPeers: Push / Pull / PushPull draw each node's k peers from its topology row
 	// (SetTopology first), not from all N nodes; RoundStats.Messages counts the exchanges.
 	FlagTopoPeers Flags = Flags(C.GOSSIP_FLAG_TOPO_PEERS)
+	// FlagAeTopoPeers: AntiEntropy draws each node's k exchange peers from its topology row by
+	// the same rule (SetTopology first); RoundStats.Messages stays the exchanges that took place.
+	FlagAeTopoPeers Flags = Flags(C.GOSSIP_FLAG_AE_TOPO_PEERS)
 )
 
 // Config mirrors gossip_config_t.  Probabilities are thresholds x / 2^32 (Threshold).

@@ -70,7 +70,7 @@ enum gossip_flags {
                                           of the binned push / pull passes — same results, A/B */
   GOSSIP_FLAG_AE_DIRECT_SCAN = 1u << 5, /* ANTIENTROPY: sparse rounds probe the peers' bitmap words
                                           directly instead of binning by tile — same results, A/B */
-  GOSSIP_FLAG_TOPO_PEERS = 1u << 6     /* PUSH / PULL / PUSHPULL: the k peers of node n are drawn from its
+  GOSSIP_FLAG_TOPO_PEERS = 1u << 6,    /* PUSH / PULL / PUSHPULL: the k peers of node n are drawn from its
                                           topology row (a sorted set, self-loops kept) instead of from all
                                           N nodes: p_j = row_n[floor(x_j * deg(n) / 2^32)] over the Philox
                                           words x_j of the uniform draw, with replacement; an empty row
@@ -81,6 +81,20 @@ enum gossip_flags {
                                           Such engines run the direct kernels (as GOSSIP_FLAG_DIRECT),
                                           sharded ones through the state all-gather round.  With FLOOD or
                                           ANTIENTROPY gossip_create returns GOSSIP_EINVAL */
+  GOSSIP_FLAG_AE_TOPO_PEERS = 1u << 7  /* ANTIENTROPY: the k exchanges of node n go to peers drawn from its
+                                          topology row by the rule of GOSSIP_FLAG_TOPO_PEERS (a sorted set,
+                                          self-loops kept, with replacement; an empty row initiates nothing
+                                          but still churns, answers and can be picked).
+                                          Churn, edge_loss and partitions apply unchanged; stats.messages
+                                          counts the exchanges that took place, an exchange with oneself
+                                          included.  The target stays the max over all nodes: on a graph
+                                          with a node nobody reaches a run does not converge.  gossip_step
+                                          (and every sharded rank, in gossip_sharded_plan) without a
+                                          topology returns GOSSIP_ESTATE; a new topology takes effect in
+                                          the next round.  Such engines run the atomic dense round and the
+                                          direct sparse scan (as "ae_dense_bin" 0 with
+                                          GOSSIP_FLAG_AE_DIRECT_SCAN).  With any other mode, or together
+                                          with GOSSIP_FLAG_TOPO_PEERS, gossip_create returns GOSSIP_EINVAL */
 };
 
 typedef struct gossip_config {
@@ -99,11 +113,14 @@ typedef struct gossip_config {
   uint32_t edge_loss;   /* random modes, FLOOD and ANTIENTROPY: P(an edge's exchange is lost)
                            per round, x / 2^32 (the reference's lossy SyncRPC,
                            main.go:77-87).  ANTIENTROPY (§2.11): a lost exchange moves neither
-                           end's row and is not counted in stats.messages                */
+                           end's row and is not counted in stats.messages; the same over the
+                           rows of GOSSIP_FLAG_AE_TOPO_PEERS (§2.12)                      */
   uint32_t partitions;  /* random modes, FLOOD and ANTIENTROPY: 0/1 = none, P > 1 = nodes split
                            into P contiguous blocks that cannot reach each other.  ANTIENTROPY:
                            the target stays the max over all nodes, so a run does not converge
-                           while a partition stands (gossip_step returns after max_rounds)  */
+                           while a partition stands (gossip_step returns after max_rounds);
+                           GOSSIP_FLAG_AE_TOPO_PEERS: a row's entries in other blocks are
+                           still drawn, and those exchanges are lost                       */
   uint32_t stall_rounds; /* 0 = off.  D > 0: the reference's deadline stall (DESIGN.md §2.9,
                            main.go:72-87: one 2 s context per neighbour, retried forever
                            once it expired).  FLOOD: a node forwards each value down its
@@ -122,7 +139,8 @@ typedef struct gossip_round_stats {
   uint64_t full_nodes;  /* nodes holding all R rumors                            */
   uint64_t alive_nodes; /* N, or the alive count after round t's churn (ANTIENTROPY) */
   uint64_t messages;    /* FLOOD: broadcast RPCs sent in round t;
-                           ANTIENTROPY: exchanges between two alive nodes;
+                           ANTIENTROPY: exchanges between two alive nodes (with
+                           GOSSIP_FLAG_AE_TOPO_PEERS too: completed exchanges, not attempts);
                            GOSSIP_FLAG_TOPO_PEERS: exchanges initiated in round t, lost attempts
                            included — k per node with a row that is not empty
                            and not stalled (PUSH: and a rumor to send); other random-mode
@@ -205,8 +223,9 @@ int gossip_set_stream(gossip_engine_t* eng, void* hip_stream);
  *                  row once fewer than 90 % of the nodes are stale (default), 0 gather them all */
 int gossip_set_param(gossip_engine_t* eng, const char* name, double value);
 
-/* Peer source of FLOOD and of the random modes created with GOSSIP_FLAG_TOPO_PEERS (other
- * random-mode engines accept a topology and draw over all N nodes all the same): directed
+/* Peer source of FLOOD, of the random modes created with GOSSIP_FLAG_TOPO_PEERS and of ANTIENTROPY
+ * created with GOSSIP_FLAG_AE_TOPO_PEERS (other random-mode and ANTIENTROPY engines accept a
+ * topology and draw over all N nodes all the same): directed
  * adjacency Topology[u] = col[row_ptr[u]..row_ptr[u+1]),
  * global node ids, n == N.  Copied; never retained.  Plain FLOOD and the random modes read each row as a set;
  * an engine created with faults or stall_rounds keeps each row as listed (order and
