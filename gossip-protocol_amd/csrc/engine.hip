@@ -184,6 +184,7 @@ struct gossip_engine {
   bool frontier = false;
   FrontierBufs fb{};
   DevBuf<uint8_t> fr_mem;
+  DevBuf<uint8_t> fp_mem;  // full-majority pull rounds: the resolved / unresolved bitmaps (fb.resolved; pulling modes)
   bool fr_valid = false;          // partial_d holds the totals of S and the bitmaps are exact
   // the round planner's shape, knobs (gossip_set_param, gossip_set_faults) and state: plan.h
   plan_cfg pl{};
@@ -659,6 +660,22 @@ bool bscan_round(const gossip_engine* e, const plan_est& x, uint32_t maj) {
   return plan_bscan_hit(&e->pl, &x, maj) >= e->pl.bscan_frac;
 }
 
+// the pull shortcut of a full-majority round: engines that keep its bitmaps (one shard, W == 1, a pulling
+// mode, peers drawn from all nodes), by plan_choose_fullpull
+bool fullpull_round(const gossip_engine* e, const plan_est& x) {
+  return e->binned && e->frontier && e->fb.resolved && plan_choose_fullpull(&e->pl, &x);
+}
+
+// (build knob: the planned path of every round on stderr, for threshold sweeps)
+inline void plan_log(uint32_t t, bool sparse, bool fullpull, const plan_est& x, uint64_t N) {
+#ifdef GOSSIP_EXP_PLAN_LOG
+  std::fprintf(stderr, "plan: round %u %s, predicted non-full share %.4f\n", t,
+               fullpull ? "fullpull" : sparse ? "sparse" : "dense", ((double)N - x.full) / (double)N);
+#else
+  (void)t, (void)sparse, (void)fullpull, (void)x, (void)N;
+#endif
+}
+
 RoundSync ring_sync(gossip_engine* e, uint32_t slot) {
   RoundSync rs;
   rs.ring = e->ring_d + (size_t)slot * (part_len(e) + 1);
@@ -686,7 +703,7 @@ int round_timer_collect(gossip_engine* e, uint32_t slot, int64_t limit) {
 // One pipelined round: its kernels (bracketed by the slot's events when timing),
 // then the snapshot of the totals into ring slot `slot` (rs).
 int launch_round_path(gossip_engine* e, uint32_t t, bool sparse, uint32_t maj, bool all_d, uint32_t filt,
-                      const RoundSync& rs, int slot, bool bscan) {
+                      const RoundSync& rs, int slot, bool bscan, bool fullpull) {
   const bool timed = e->timing && slot >= 0;
   if (timed) {
     if (int rc = round_timer_collect(e, (uint32_t)slot, INT64_MAX)) return rc;
@@ -705,7 +722,10 @@ int launch_round_path(gossip_engine* e, uint32_t t, bool sparse, uint32_t maj, b
     fb.bregions = bs_regions(e->N);
     fb.btabT = fb.btab + bs_tab_bytes(e->N) / 4;  // (the second half of bs_tab_bytes)
   }
-  if (sparse)
+  if (fullpull)  // full-majority pull shortcut, whatever the sparse / dense choice
+    HIP_OK(e, launch_frontier_fullpull(fb, e->S, e->N, e->partial_d, e->R, e->k, t, e->key0, e->key1, e->mode, e->fa,
+                                       e->cfg.flags, e->stream));
+  else if (sparse)
     HIP_OK(e, launch_frontier_round(fb, e->S, e->N, e->partial_d, e->R, e->k, t, e->key0, e->key1, e->mode, maj,
                                     !all_d ? kSparseFlags : (maj == 0 && e->sparse_direct ? kSparseDirect : kSparseAllD),
                                     e->fa, e->cfg.flags, rs, e->stream));
@@ -715,7 +735,7 @@ int launch_round_path(gossip_engine* e, uint32_t t, bool sparse, uint32_t maj, b
   if (timed) {
     HIP_OK(e, hipEventRecord(e->evr[slot][1], e->stream));
     e->evr_round[slot] = t;
-    e->evr_kind[slot] = sparse ? 4 : 3;
+    e->evr_kind[slot] = sparse || fullpull ? 4 : 3;
   }
   HIP_OK(e, launch_round_snapshot(e->partial_d, rs, e->stream));
   // stall streaks after round t (gossip_round_commit does it for rounds not run from here)
@@ -781,8 +801,10 @@ int step_planned(gossip_engine* e, uint32_t max_rounds, gossip_round_stats_t* st
       const uint32_t slot = launched % kRing;
       const RoundSync rs = ring_sync(e, slot);
       want[slot] = rs.seq;
+      const bool fullpull = fullpull_round(e, x);
+      plan_log(t0 + launched, sparse, fullpull, x, e->N);
       if (int rc = launch_round_path(e, t0 + launched, sparse, maj, all_d, filt, rs, (int)slot,
-                                     sparse && bscan_round(e, x, maj)))
+                                     sparse && bscan_round(e, x, maj), fullpull))
         return rc;
       ++launched;
     }
@@ -1173,7 +1195,7 @@ int compute_round(gossip_engine* e, const uint64_t* gathered) {
     const uint32_t filt = plan_dense_filter(&e->pl, &x, plan_filter_frac(&e->pl));
     if ((rc = timer_begin(e, 0))) return rc;
     if ((rc = launch_round_path(e, e->t, sparse, maj, all_d, filt,
-                                ring_sync(e, 0), -1, sparse && bscan_round(e, x, maj))))
+                                ring_sync(e, 0), -1, sparse && bscan_round(e, x, maj), fullpull_round(e, x))))
       return rc;
     return timer_end(e, 0);  // stats are fused into the round kernels
   } else if (e->rep_planned) {  // replicated dense round: the one-GPU round over the whole image
@@ -1546,6 +1568,10 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
       e->bb.nzb = e->fb.nzb;
       e->bb.fullb = e->fb.fullb;
       e->frontier = true;
+      if (plan_pulls(&e->pl)) {  // (binned: one shard, W == 1, peers drawn from all nodes)
+        if (!alloc(e->fp_mem, fullpull_bytes(e->N))) return bail(GOSSIP_ENOMEM);
+        fullpull_carve(e->N, e->fp_mem, &e->fb);
+      }
     }
     if (e->ring_h.alloc(kRing * (part_len(e) + 1), hipHostMallocMapped) != hipSuccess ||
         hipHostGetDevicePointer((void**)&e->ring_d, e->ring_h, 0) != hipSuccess) {

@@ -52,6 +52,13 @@ struct FrontierBufs {
   uint16_t* btabT;   // [btiles + 1][bregions]: btab transposed (K1b reads a tile's column contiguously)
   uint32_t btiles, bregions;
   uint64_t id0;      // global id of node 0 of these arrays (a shard's first node; 0 on one GPU): the hash uses global ids
+  // full-majority pull rounds (launch_frontier_fullpull; null: the engine keeps none): bit n of
+  // resolved = a non-full node that pulls from a full peer (S_{t+1}[n] is the full mask), of unres =
+  // a non-full node that does not; both rewritten whole by every such round.  fpc[0]: nodes in
+  // unres, fpc[1]: the round found S_t converged (no kernel of it touches anything).
+  uint64_t* resolved;
+  uint64_t* unres;
+  uint32_t* fpc;
 };
 
 uint32_t frontier_glog(uint64_t N);
@@ -113,5 +120,23 @@ hipError_t launch_frontier_round(const FrontierBufs& f, uint64_t* S, uint64_t N,
                                  uint32_t k, uint32_t t, uint32_t key0, uint32_t key1, uint32_t mode, uint32_t maj,
                                  uint32_t dmode, const Faults& fa, uint32_t flags, const RoundSync& rs,
                                  hipStream_t st);
+
+// Full-majority pull round (PULL / PUSHPULL), in place on S; exact for any state.
+// In the pulling modes S_{t+1}[n] = S_t[n] | OR_j S_t[p_j(n)] | pushes, every read of S_t: a node
+// with a full pulled peer on an edge that is not lost ends full whatever else reaches it, and it
+// can tell from its own k draws and k bits of fullb.  Three passes:
+//   resolve  every wave that holds a non-full node draws those nodes' peers and probes fullb:
+//            bitmaps resolved / unres (one word per wave), no write to S or D;
+//   scan     the queued frontier scan with unres as its rare set: an edge is kept if its node is
+//            unresolved (its pull) or, when the mode pushes, its peer is (the push into it);
+//            deltas into D with dirty flags; returns at once when nothing is unresolved;
+//   commit   groups with a resolved node or a dirty flag: S = full mask where resolved, S |= D
+//            where dirty, both bitmap words, stats deltas into the running totals.
+// f.resolved / f.unres / f.fpc must be set (fullpull_bytes, fullpull_carve).
+size_t fullpull_bytes(uint64_t N);
+void fullpull_carve(uint64_t N, void* base, FrontierBufs* f);
+hipError_t launch_frontier_fullpull(const FrontierBufs& f, uint64_t* S, uint64_t N, uint64_t* partial, uint32_t R,
+                                    uint32_t k, uint32_t t, uint32_t key0, uint32_t key1, uint32_t mode,
+                                    const Faults& fa, uint32_t flags, hipStream_t st);
 
 }  // namespace gossip

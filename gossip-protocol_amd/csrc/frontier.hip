@@ -64,8 +64,10 @@ __device__ __forceinline__ uint64_t word_valid(uint64_t w, uint64_t N) {
   return N >= lo + 64 ? ~0ull : ((1ull << (N - lo)) - 1ull);
 }
 
+// MAJ 2: the unresolved set of a full-majority pull round (bits past N are zero there too)
 template <int MAJ>
 __device__ __forceinline__ uint64_t rare_word(const FrontierBufs& f, uint64_t w, uint64_t N) {
+  if (MAJ == 2) return f.unres[w];
   return MAJ ? (~f.fullb[w] & word_valid(w, N)) : f.nzb[w];
 }
 
@@ -1025,6 +1027,340 @@ __global__ __launch_bounds__(kCommitThreads) void frontier_commit_kernel(Frontie
   gs.flush(partial, R, cnt, red);
 }
 
+// ---- Full-majority pull rounds (frontier.h: launch_frontier_fullpull) ----
+constexpr int kFpThreads = 1024;
+constexpr uint32_t kFpGrid = 512;  // persistent resolve blocks (2 per CU: 12 KiB of LDS each)
+constexpr int kFpUnroll = 2;       // nodes per lane per resolve step
+
+// Pass 1.  A node range per block and the non-full words of 32K nodes staged in LDS, as in the
+// scan; the two result words of each wave go through LDS too and leave as whole chunks.  A wave
+// without a non-full node draws nothing.  All fullb probes of a batch (kFpUnroll nodes x 4 peers
+// per lane) are issued before any is consumed.
+template <bool FAULTS>
+__global__ __launch_bounds__(kFpThreads, FAULTS ? 4 : 8) void frontier_fp_resolve_kernel(FrontierBufs f, uint64_t N, uint32_t R,
+                                                                            uint32_t k, uint32_t t, uint32_t key0,
+                                                                            uint32_t key1, uint64_t per_block,
+                                                                            const uint64_t* partial, Faults fa) {
+  __shared__ uint64_t rws[kRwWords], res_s[kRwWords], unr_s[kRwWords];
+  __shared__ uint32_t ucnt;
+  if (rare_count(partial, N, R, 1u) == 0) {  // converged: the later passes must not run on stale bitmaps
+    if (blockIdx.x == 0 && threadIdx.x == 0) f.fpc[1] = 1u;
+    return;
+  }
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  if (tid == 0) ucnt = 0;
+  const uint32_t nm1 = (uint32_t)(N - 1);
+  const uint32_t b0 = blockIdx.x * (uint32_t)per_block, b1 = (uint32_t)min<uint64_t>((uint64_t)b0 + per_block, N);
+  uint32_t un_wave = 0;  // unresolved nodes of this wave's words (lane 0)
+  for (uint32_t c0 = b0; c0 < b1; c0 += kRwWords * 64) {
+    const uint32_t c1 = min(c0 + kRwWords * 64, b1), nw = (c1 - c0 + 63) >> 6;
+    __syncthreads();  // previous chunk written out
+    for (uint32_t i = tid; i < nw; i += kFpThreads) rws[i] = rare_word<1>(f, (c0 >> 6) + i, N);
+    __syncthreads();
+    for (uint32_t base = c0; base < c1; base += kFpThreads * kFpUnroll) {
+      bool rn[kFpUnroll], res[kFpUnroll];
+      bool any = false;
+#pragma unroll
+      for (int u = 0; u < kFpUnroll; ++u) {
+        const uint32_t n = base + u * kFpThreads + tid;
+        rn[u] = n < c1 && ((rws[(n - c0) >> 6] >> lane) & 1ull);
+        res[u] = false;
+        any = any || rn[u];
+      }
+      if (__ballot(any)) {
+        for (uint32_t q = 0; q * 4 < k; ++q) {  // four draws per cipher call
+          uint64_t fw[kFpUnroll][4];
+          uint32_t pb[kFpUnroll][4];
+#pragma unroll
+          for (int u = 0; u < kFpUnroll; ++u) {
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+              fw[u][j] = 0ull;
+              pb[u][j] = 0u;
+            }
+            if (!rn[u] || res[u]) continue;
+            const uint32_t n = base + u * kFpThreads + tid;
+            const u32x4 r4 = philox4x32_10(u32x4{n, t, 0u, q}, key0, key1);
+            u32x4 lw{0, 0, 0, 0};
+            Reach rc{0u, 0xFFFFFFFFu};
+            if (FAULTS) {
+              if (fa.loss) lw = loss_draws(n, t, q, key0, key1);
+              rc = reach_of(n, fa);
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+              if (q * 4 + j >= k) break;
+              const uint32_t p = peer_from_word(lane_of(r4, j), nm1, n);
+              if (FAULTS && edge_lost(fa, rc, p, lane_of(lw, j))) continue;
+              fw[u][j] = f.fullb[p >> 6];  // p < N: always a valid word
+              pb[u][j] = p & 63u;
+            }
+          }
+#pragma unroll
+          for (int u = 0; u < kFpUnroll; ++u)
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j)
+              if ((fw[u][j] >> pb[u][j]) & 1ull) res[u] = true;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kFpUnroll; ++u) {
+        const uint32_t n0 = base + u * kFpThreads + (tid & ~63u);  // the wave's first node (wave-uniform)
+        const uint64_t rb = __ballot(rn[u] && res[u]), ub = __ballot(rn[u] && !res[u]);
+        if (lane == 0 && n0 < c1) {
+          res_s[(n0 - c0) >> 6] = rb;
+          unr_s[(n0 - c0) >> 6] = ub;
+          un_wave += (uint32_t)__popcll(ub);
+        }
+      }
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < nw; i += kFpThreads) {
+      f.resolved[(c0 >> 6) + i] = res_s[i];
+      f.unres[(c0 >> 6) + i] = unr_s[i];
+    }
+  }
+  if (lane == 0 && un_wave) atomicAdd(&ucnt, un_wave);
+  __syncthreads();
+  if (tid == 0 && ucnt) atomicAdd(&f.fpc[0], ucnt);
+}
+
+// the two summaries of the unresolved set (frontier_summary_kernel's layout of blocks)
+__global__ __launch_bounds__(256) void frontier_fp_summary_kernel(FrontierBufs f, uint64_t N) {
+  if (f.fpc[0] == 0) return;
+  const uint32_t b1 = (f.summ_words + 255) / 256;
+  if (blockIdx.x >= b1)
+    summ2_body<2>(f, (blockIdx.x - b1) * 256 + threadIdx.x, N);
+  else
+    summary_body<2>(f, N);
+}
+
+// Pass 2: queued edges as in scan_flush (x = node - block base | unresolved(n) << 24 | summary
+// hit(p) << 25, y = p).  A hit is confirmed in the summaries' source, unres.  An unresolved node
+// pulls S_t[p] (p is not full: the node would be resolved); a node of any class pushes S_t[n]
+// into an unresolved peer.  Edges into full or resolved targets carry nothing the commit needs.
+template <int MODE>
+__device__ __forceinline__ void fp_flush(const uint2* qw, uint32_t nf, const FrontierBufs& f,
+                                         const uint64_t* __restrict__ S, uint32_t b0, bool mid, uint32_t lane) {
+  constexpr bool kPush = (MODE & 1) != 0;
+  constexpr int kE = kQFlush / 64;
+  uint32_t n[kE], p[kE];
+  bool un[kE], hit[kE];
+#pragma unroll
+  for (int e = 0; e < kE; ++e) {
+    const uint32_t i = lane + 64u * e;
+    const uint2 q = i < nf ? qw[i] : uint2{0u, 0u};
+    n[e] = b0 + (q.x & 0xFFFFFFu);
+    un[e] = (q.x >> 24) & 1u;
+    hit[e] = kPush && ((q.x >> 25) & 1u);
+    p[e] = q.y;
+  }
+  if (f.glog && mid) {
+    uint32_t sw[kE];
+#pragma unroll
+    for (int e = 0; e < kE; ++e) sw[e] = hit[e] ? f.summ2[p[e] >> (f.g2log + 5)] : 0u;
+#pragma unroll
+    for (int e = 0; e < kE; ++e) hit[e] = hit[e] && ((sw[e] >> ((p[e] >> f.g2log) & 31u)) & 1u);
+  }
+  if (f.glog) {
+    uint64_t rw[kE];
+#pragma unroll
+    for (int e = 0; e < kE; ++e) rw[e] = hit[e] ? f.unres[p[e] >> 6] : 0ull;
+#pragma unroll
+    for (int e = 0; e < kE; ++e) hit[e] = hit[e] && ((rw[e] >> (p[e] & 63u)) & 1ull);
+  }
+  uint64_t x[kE], vp[kE];
+#pragma unroll
+  for (int e = 0; e < kE; ++e) {
+    const bool any = un[e] || hit[e];  // (an empty slot: neither)
+    x[e] = any ? scan_ld(&S[n[e]]) : 0ull;
+    vp[e] = any ? scan_ld(&S[p[e]]) : 0ull;
+  }
+  uint64_t dpush[kE], dpull[kE];
+#pragma unroll
+  for (int e = 0; e < kE; ++e) {
+    dpush[e] = hit[e] ? x[e] & ~vp[e] : 0ull;
+    dpull[e] = un[e] ? vp[e] & ~x[e] : 0ull;
+  }
+#pragma unroll
+  for (int e = 0; e < kE; ++e) {
+    if (dpush[e]) {
+      atomicOr((unsigned long long*)&f.D[p[e]], (unsigned long long)dpush[e]);
+      f.dirtyD[p[e] >> 6] = 1;
+    }
+    if (dpull[e]) {
+      atomicOr((unsigned long long*)&f.D[n[e]], (unsigned long long)dpull[e]);
+      f.dirtyD[n[e] >> 6] = 1;
+    }
+  }
+}
+
+template <int MODE, bool FAULTS>
+__global__ __launch_bounds__(kScanThreads, kScanWaves) void frontier_fp_scan_kernel(FrontierBufs f, const uint64_t* S,
+                                                                         uint64_t N, uint32_t k, uint32_t t,
+                                                                         uint32_t key0, uint32_t key1,
+                                                                         uint64_t per_block, Faults fa) {
+  __shared__ uint4 summ4[kSummBits / 128];
+  __shared__ uint64_t rws[kRwWords];
+  __shared__ uint2 qs[(kScanThreads / 64) * kQCap];
+  const uint32_t nun = f.fpc[0];
+  if (nun == 0) return;  // every non-full node is resolved (or S_t is converged)
+  constexpr bool kPush = (MODE & 1) != 0;
+  // the mid-level summary once the LDS one is that saturated (use_mid, from the unresolved count)
+  const float ur = fminf((float)nun / (float)N, 0.999999f);
+  const bool mid = f.summ2 && 1.0f - __expf((float)(1u << f.glog) * log1pf(-ur)) >= f.mid_frac;
+  const uint32_t* summ = (const uint32_t*)summ4;
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  uint2* qw = qs + (tid >> 6) * kQCap;  // this wave's queue
+  const uint32_t n4 = (f.summ_words + 3) / 4;
+  if (kPush)
+    for (uint32_t i = tid; i < n4; i += kScanThreads) summ4[i] = ((const uint4*)f.summ)[i];
+  const uint32_t nm1 = (uint32_t)(N - 1), glog = f.glog;
+  auto summ_bit = [&](uint32_t p) -> bool { return (summ[p >> (glog + 5)] >> ((p >> glog) & 31u)) & 1u; };
+  const uint32_t b0 = blockIdx.x * (uint32_t)per_block, b1 = (uint32_t)min<uint64_t>((uint64_t)b0 + per_block, N);
+  uint32_t qn = 0;  // entries in this wave's queue (wave-uniform)
+  for (uint32_t c0 = b0; c0 < b1; c0 += kRwWords * 64) {
+    const uint32_t c1 = min(c0 + kRwWords * 64, b1);
+    __syncthreads();  // previous chunk done with rws (first chunk: the summary is in LDS)
+    for (uint32_t i = tid; i < ((c1 - c0 + 63) >> 6); i += kScanThreads) rws[i] = rare_word<2>(f, (c0 >> 6) + i, N);
+    __syncthreads();
+    for (uint32_t base = c0; base < c1; base += kScanThreads * kScanUnroll) {
+      bool un[kScanUnroll], act[kScanUnroll];
+      bool any = false;
+#pragma unroll
+      for (int u = 0; u < kScanUnroll; ++u) {
+        const uint32_t n = base + u * kScanThreads + tid;
+        const bool valid = n < c1;
+        un[u] = valid && ((rws[(n - c0) >> 6] >> lane) & 1ull);
+        act[u] = valid && (un[u] || kPush);  // a pull-only round moves nothing through the other nodes
+        any = any || act[u];
+      }
+      if (!__ballot(any)) continue;
+      for (uint32_t q = 0; q * 4 < k; ++q) {  // four draws per cipher call
+        uint32_t pp[kScanUnroll][4], cand[kScanUnroll];
+        bool anyc = false;
+#pragma unroll
+        for (int u = 0; u < kScanUnroll; ++u) {
+          const uint32_t n = base + u * kScanThreads + tid;
+          cand[u] = 0;  // bit j: edge 4q + j is live and has an unresolved or possibly unresolved end
+          if (act[u]) {
+            const u32x4 r4 = philox4x32_10(u32x4{n, t, 0u, q}, key0, key1);
+            u32x4 lw{0, 0, 0, 0};
+            Reach rc{0u, 0xFFFFFFFFu};
+            if (FAULTS) {
+              if (fa.loss) lw = loss_draws(n, t, q, key0, key1);
+              rc = reach_of(n, fa);
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+              pp[u][j] = 0;
+              if (q * 4 + j >= k) continue;
+              pp[u][j] = peer_from_word(lane_of(r4, j), nm1, n);
+              const bool lost = FAULTS && edge_lost(fa, rc, pp[u][j], lane_of(lw, j));
+              if (!lost && (un[u] || (kPush && summ_bit(pp[u][j])))) cand[u] |= 1u << j;
+            }
+          }
+          anyc = anyc || cand[u] != 0u;
+        }
+        if (!__ballot(anyc)) continue;
+#pragma unroll
+        for (int u = 0; u < kScanUnroll; ++u) {
+          const uint32_t n = base + u * kScanThreads + tid;
+#pragma unroll
+          for (uint32_t j = 0; j < 4; ++j) {
+            const bool c = (cand[u] >> j) & 1u;
+            const uint64_t m = __ballot(c);
+            if (!m) continue;
+            if (c) {
+              const uint32_t pos =
+                  qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+              const bool h = kPush && summ_bit(pp[u][j]);
+              qw[pos] = uint2{(n - b0) | (uint32_t)un[u] << 24 | (uint32_t)h << 25, pp[u][j]};
+            }
+            qn += (uint32_t)__popcll(m);
+            if (qn >= kQFlush) {
+              __builtin_amdgcn_wave_barrier();
+              fp_flush<MODE>(qw, kQFlush, f, S, b0, mid, lane);
+              qn -= kQFlush;  // (< 64 left: move them to the front)
+              const uint2 rest = lane < qn ? qw[kQFlush + lane] : uint2{0u, 0u};
+              __builtin_amdgcn_wave_barrier();
+              if (lane < qn) qw[lane] = rest;
+              __builtin_amdgcn_wave_barrier();
+            }
+          }
+        }
+      }
+    }
+  }
+  if (qn) {
+    __builtin_amdgcn_wave_barrier();
+    fp_flush<MODE>(qw, qn, f, S, b0, mid, lane);
+  }
+}
+
+// Pass 3: frontier_commit_kernel's walk over the groups that have a resolved node or a dirty flag.
+__global__ __launch_bounds__(kCommitThreads) void frontier_fp_commit_kernel(FrontierBufs f, uint64_t* __restrict__ S,
+                                                                             uint64_t N, uint64_t* __restrict__ partial,
+                                                                             uint32_t R, uint32_t flags) {
+  __shared__ uint32_t cnt[64];
+  __shared__ uint64_t red[3][kCommitThreads / 64];
+  if (f.fpc[1]) return;  // S_t was converged: the bitmaps of this round were not written
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid < 64) cnt[tid] = 0;
+  __syncthreads();
+  const uint64_t fm = full_mask1(R), ngroups = (N + 63) >> 6;
+  const bool do_hash = (flags & 1u) != 0;
+  GroupStats gs;
+  for (uint64_t c = (uint64_t)blockIdx.x * (kCommitThreads / 64) + wave; (c << kCommitChunkLog) < ngroups;
+       c += (uint64_t)gridDim.x * (kCommitThreads / 64)) {
+    const uint64_t gl = (c << kCommitChunkLog) + lane;
+    const bool gv = lane < (1u << kCommitChunkLog) && gl < ngroups;
+    const uint8_t fd = gv ? f.dirtyD[gl] : 0;
+    const uint64_t rsw = gv ? f.resolved[gl] : 0ull;
+    if (fd) f.dirtyD[gl] = 0;
+    const uint64_t mD = __ballot(fd != 0);
+    uint64_t mask = __ballot(fd != 0 || rsw != 0ull);
+    while (mask) {
+      uint32_t gi[kCommitUnroll];
+      uint32_t cntg = 0;
+#pragma unroll
+      for (int u = 0; u < kCommitUnroll; ++u) {
+        gi[u] = mask ? (uint32_t)__builtin_ctzll(mask) : 64u;
+        if (mask) {
+          mask &= mask - 1;
+          ++cntg;
+        }
+      }
+      uint64_t d[kCommitUnroll], old[kCommitUnroll], rs[kCommitUnroll];
+#pragma unroll
+      for (int u = 0; u < kCommitUnroll; ++u) rs[u] = gi[u] < 64 ? f.resolved[(c << kCommitChunkLog) + gi[u]] : 0ull;
+#pragma unroll
+      for (int u = 0; u < kCommitUnroll; ++u) {
+        const uint64_t n = (((c << kCommitChunkLog) + (gi[u] & 63u)) << 6) + lane;
+        const bool valid = gi[u] < 64 && n < N;
+        const bool hd = gi[u] < 64 && ((mD >> gi[u]) & 1ull);
+        d[u] = valid && hd ? f.D[n] : 0ull;
+        old[u] = valid ? S[n] : 0ull;
+      }
+#pragma unroll
+      for (int u = 0; u < kCommitUnroll; ++u) {
+        if ((uint32_t)u >= cntg) break;
+        const uint64_t g = (c << kCommitChunkLog) + gi[u];
+        const uint64_t n = (g << 6) + lane;
+        const bool valid = n < N;
+        const uint64_t nw = ((rs[u] >> lane) & 1ull) ? fm : (old[u] | d[u]);  // (resolved bits are valid nodes)
+        // whole 8-word (64 B) chunks, as in the commit
+        const uint32_t sh = lane & ~7u;
+        const uint64_t chg = __ballot(valid && nw != old[u]), dz = __ballot(d[u] != 0);
+        if (valid && ((chg >> sh) & 0xFFull)) S[n] = nw;
+        if (valid && ((dz >> sh) & 0xFFull)) f.D[n] = 0;
+        gs.add(f, g, n, valid, old[u], nw, fm, do_hash, lane);
+      }
+    }
+  }
+  gs.flush(partial, R, cnt, red);
+}
+
 // Client broadcast with exact running totals and bitmaps (atomics: two rumors
 // may share an origin; each atomic's own old value makes every delta exact).
 __global__ void frontier_inject_kernel(FrontierBufs f, uint64_t* S, uint64_t N, uint64_t* partial, uint32_t R,
@@ -1200,6 +1536,55 @@ hipError_t launch_frontier_round(const FrontierBufs& f, uint64_t* S, uint64_t N,
   }
   const hipError_t ce = launch_frontier_commit(f, S, N, partial, R, dmode, flags, st);
   return ce;  // the engine enqueues the round's snapshot (round.h) after its timing event
+}
+
+size_t fullpull_bytes(uint64_t N) { return 2 * al256((N + 63) / 64 * 8) + 256; }
+
+void fullpull_carve(uint64_t N, void* base, FrontierBufs* f) {
+  char* p = (char*)base;
+  f->resolved = (uint64_t*)p;
+  p += al256((N + 63) / 64 * 8);
+  f->unres = (uint64_t*)p;
+  p += al256((N + 63) / 64 * 8);
+  f->fpc = (uint32_t*)p;
+}
+
+hipError_t launch_frontier_fullpull(const FrontierBufs& f, uint64_t* S, uint64_t N, uint64_t* partial, uint32_t R,
+                                    uint32_t k, uint32_t t, uint32_t key0, uint32_t key1, uint32_t mode,
+                                    const Faults& fa, uint32_t flags, hipStream_t st) {
+  if (N == 0) return hipSuccess;
+  if ((mode != 2 && mode != 3) || !f.resolved || !f.unres || !f.fpc) return hipErrorInvalidValue;
+  const bool faults = fa.any();
+  if (const hipError_t me = hipMemsetAsync(f.fpc, 0, 8, st)) return me;
+  const uint64_t chunks = (N + kFpThreads - 1) / kFpThreads;
+  {  // contiguous node range per block, a multiple of the block width (whole bitmap words per wave)
+    const uint32_t grid = (uint32_t)(chunks < kFpGrid ? chunks : kFpGrid);
+    const uint64_t per = ((N + grid - 1) / grid + kFpThreads - 1) / kFpThreads * kFpThreads;
+    if (faults)
+      frontier_fp_resolve_kernel<true><<<grid, kFpThreads, 0, st>>>(f, N, R, k, t, key0, key1, per, partial, fa);
+    else
+      frontier_fp_resolve_kernel<false><<<grid, kFpThreads, 0, st>>>(f, N, R, k, t, key0, key1, per, partial, fa);
+  }
+  if (mode == 3)  // (a pull-only scan tests no peer)
+    frontier_fp_summary_kernel<<<(f.summ_words + 255) / 256 + (f.summ2_words + 255) / 256, 256, 0, st>>>(f, N);
+  const uint32_t grid = (uint32_t)(chunks < kScanGrid ? chunks : kScanGrid);
+  const uint64_t per = ((N + grid - 1) / grid + kScanThreads - 1) / kScanThreads * kScanThreads;
+  if (mode == 3) {
+    if (faults)
+      frontier_fp_scan_kernel<3, true><<<grid, kScanThreads, 0, st>>>(f, S, N, k, t, key0, key1, per, fa);
+    else
+      frontier_fp_scan_kernel<3, false><<<grid, kScanThreads, 0, st>>>(f, S, N, k, t, key0, key1, per, fa);
+  } else {
+    if (faults)
+      frontier_fp_scan_kernel<2, true><<<grid, kScanThreads, 0, st>>>(f, S, N, k, t, key0, key1, per, fa);
+    else
+      frontier_fp_scan_kernel<2, false><<<grid, kScanThreads, 0, st>>>(f, S, N, k, t, key0, key1, per, fa);
+  }
+  const uint64_t wchunks = (((N + 63) >> 6) + (1u << kCommitChunkLog) - 1) >> kCommitChunkLog;  // one per wave
+  const uint64_t cblocks = (wchunks + kCommitThreads / 64 - 1) / (kCommitThreads / 64);
+  frontier_fp_commit_kernel<<<(uint32_t)(cblocks < kCommitMaxBlocks ? cblocks : kCommitMaxBlocks), kCommitThreads, 0,
+                              st>>>(f, S, N, partial, R, flags);
+  return hipGetLastError();
 }
 
 }  // namespace gossip

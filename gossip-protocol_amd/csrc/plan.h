@@ -34,7 +34,14 @@ typedef struct plan_cfg {
   uint32_t glog;            /* the rare summary: 2^glog nodes per bit */
   int has_mid;              /* ... and whether it has a mid level */
   int rep_img_ok;           /* state: the image holds S_t of every node (the last round was replicated) */
+  double fullpull_frac;     /* pulling modes: a full-majority round with at most this share of non-full nodes resolves
+                             * them from their own draws (plan_choose_fullpull) */
 } plan_cfg;
+
+/* (build knob for sweeps and A/B runs; 0 = never) */
+#ifndef GOSSIP_FULLPULL_FRAC
+#define GOSSIP_FULLPULL_FRAC 0.3
+#endif
 
 static inline void plan_defaults(plan_cfg* c) {
   c->sparse_frac = 1.0 / 16;
@@ -47,6 +54,7 @@ static inline void plan_defaults(plan_cfg* c) {
   c->link_gbps = 76.0;
   c->mid_frac = 0.5;
   c->bscan_frac = 0.6;
+  c->fullpull_frac = GOSSIP_FULLPULL_FRAC;
 }
 
 /* Totals the path choice needs: full and nonzero counts, per-rumor infected. */
@@ -127,6 +135,17 @@ static inline int plan_choose_sparse(const plan_cfg* c, const plan_est* x, uint3
   *maj = c->can_sparse && hi < lo ? 1u : 0u;
   *all_d = c->can_sparse && rare * (double)c->k >= c->alld_frac * (double)c->N;
   return c->can_sparse && rare <= plan_sparse_frac(c) * (double)c->N;
+}
+
+/* One-shard pulling modes (the caller checks what it can run): a full-majority round whose non-full
+ * share is at most fullpull_frac takes the pull shortcut (a non-full node with a full
+ * pulled peer ends full), whatever plan_choose_sparse says.  A sparse_frac set by gossip_set_param caps
+ * the share (0 keeps such rounds dense); set to 1 it sends every full-majority round there. */
+static inline int plan_choose_fullpull(const plan_cfg* c, const plan_est* x) {
+  const double lo = x->nz, hi = (double)c->N - x->full;
+  double frac = c->fullpull_frac;
+  if (c->sparse_frac_set) frac = c->sparse_frac >= 1.0 ? 1.0 : plan_min(frac, c->sparse_frac);
+  return c->can_sparse && plan_pulls(c) && hi < lo && hi <= frac * (double)c->N;
 }
 
 /* the share of peers that hit a summary bit of 2^glog nodes when a share r of the nodes is rare */

@@ -191,7 +191,10 @@ int gossip_set_stream(gossip_engine_t* eng, void* hip_stream);
  * otherwise choose by cost; tests/test_abi.py pins this list):
  *   "sparse_frac"  random modes: a round runs sparse when the rare class is at most this fraction
  *                  of N (default 1/16; sharded 1/4, or 1/25 before exchange rounds; < 0 never,
- *                  >= 1 always; overrides link_gbps)
+ *                  >= 1 always; overrides link_gbps).  One-shard PULL / PUSHPULL engines run a
+ *                  full-majority round with at most 0.3 N nodes not full on the pull shortcut
+ *                  (DESIGN.md §3.3); a value set here caps that share, and >= 1 sends every
+ *                  full-majority round there
  *   "alld_frac"    sparse rounds commit every group's D once k x rare >= this x N (default 1/128)
  *   "sparse_direct"  such rounds with an empty majority OR the pushes into empty peers straight
  *                  into the state (default 1; 0: into D)
@@ -329,7 +332,8 @@ int gossip_philox_device(gossip_engine_t* eng, const uint32_t* ctr4, const uint3
  * 1 = the separate stats kernel (direct path only; fused in the binned path),
  * 2 = ANTIENTROPY sparse rounds' kernels (their stats pass counts under 1; dense rounds under 0),
  * 3 = dense rounds of a binned engine: emit + transpose + serve + apply of each round,
- * 4 = sparse (frontier) rounds of a binned engine: summary + scan + commit of each round,
+ * 4 = sparse (frontier) rounds of a binned engine: summary + scan + commit of each round (the pull
+ *     shortcut's rounds count here: resolve + summary + scan + commit),
  * 5 = placement trial rounds of a binned engine's record slab (param place_tries; before its
  *     first round). */
 int gossip_kernel_time(const gossip_engine_t* eng, uint32_t which, double* total_ms, uint64_t* launches);
