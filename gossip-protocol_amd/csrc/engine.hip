@@ -29,6 +29,7 @@
 #include <cmath>
 #include <immintrin.h>
 #include "kernels.h"
+#include "monger.h"
 #include "multi.h"
 #include "philox.h"
 #include "topo_peers.h"
@@ -100,6 +101,10 @@ struct gossip_engine {
   bool has_topo = false;
   bool topo_peers = false;  // GOSSIP_FLAG_TOPO_PEERS: random modes draw their peers from the rows
   bool ae_topo = false;     // GOSSIP_FLAG_AE_TOPO_PEERS: ANTIENTROPY exchanges go to peers from the rows (§2.12)
+  // GOSSIP_FLAG_MONGER: H_t / H_{t+1}, the rumors each node is still hot on, [W][N]
+  bool monger = false;
+  uint32_t cool = 0, blind = 0;  // gossip_set_monger
+  DevBuf<uint64_t> hot, hot_next;
   // stall mode, random modes: streak per node, all N nodes on every shard
   DevBuf<uint8_t> stall_d;
   // FLOOD with faults, one shard: per out-edge pending values and first senders
@@ -1217,8 +1222,14 @@ int compute_round(gossip_engine* e, const uint64_t* gathered) {
     // timer 0 covers the whole S_t -> S_{t+1} transform (seed copy + round kernel)
     if ((rc = timer_begin(e, 0))) return rc;
     HIP_OK(e, hipMemcpyAsync(e->Snext, e->S, bytes, hipMemcpyDeviceToDevice, e->stream));
-    if (e->topo_peers) HIP_OK(e, launch_round_topo(a, e->stream));  // peers from the rows
-    else HIP_OK(e, launch_round_random(a, e->stream));
+    if (e->monger) {  // rumor mongering: H moves with S
+      HIP_OK(e, hipMemcpyAsync(e->hot_next, e->hot, bytes, hipMemcpyDeviceToDevice, e->stream));
+      HIP_OK(e, launch_round_monger(MongerArgs{a, e->hot, e->hot_next, e->cool, e->blind, e->topo_peers}, e->stream));
+    } else if (e->topo_peers) {
+      HIP_OK(e, launch_round_topo(a, e->stream));  // peers from the rows
+    } else {
+      HIP_OK(e, launch_round_random(a, e->stream));
+    }
     if ((rc = timer_end(e, 0))) return rc;
   }
   if ((rc = timer_begin(e, 1))) return rc;
@@ -1244,6 +1255,7 @@ void rotate(gossip_engine* e) {
   } else if (!e->binned) {  // binned rounds run in place
     e->cur ^= 1;
     bind_slices(e);
+    if (e->monger) e->hot.swap(e->hot_next);
   }
 }
 
@@ -1377,6 +1389,10 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
                      "FLOOD sends to the whole row)";
     return GOSSIP_EINVAL;
   }
+  if ((cfg->flags & GOSSIP_FLAG_MONGER) && cfg->mode != GOSSIP_MODE_PUSH) {
+    g_create_error = "GOSSIP_FLAG_MONGER applies to PUSH (rumor mongering pushes the hot rumors; DESIGN.md §2.13)";
+    return GOSSIP_EINVAL;
+  }
   const uint32_t G = cfg->shard_count ? cfg->shard_count : 1;
   if (cfg->shard_rank >= G) {
     g_create_error = "shard_rank >= shard_count";
@@ -1385,6 +1401,10 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
   if (cfg->stall_rounds > 16) {
     g_create_error = "stall_rounds must be in [0, 16]";
     return GOSSIP_EINVAL;
+  }
+  if ((cfg->flags & GOSSIP_FLAG_MONGER) && (cfg->stall_rounds || G > 1)) {
+    g_create_error = "GOSSIP_FLAG_MONGER runs on one shard and without stall_rounds (DESIGN.md §2.13)";
+    return GOSSIP_ENOTSUP;
   }
   const bool faulty = cfg->edge_loss || cfg->partitions > 1 || cfg->stall_rounds;
   if (cfg->stall_rounds && cfg->mode == GOSSIP_MODE_ANTIENTROPY) {
@@ -1440,8 +1460,9 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
   e->flood_edges = e->mode == GOSSIP_MODE_FLOOD && faulty;
   e->topo_peers = (cfg->flags & GOSSIP_FLAG_TOPO_PEERS) != 0;
   e->ae_topo = (cfg->flags & GOSSIP_FLAG_AE_TOPO_PEERS) != 0;
+  e->monger = (cfg->flags & GOSSIP_FLAG_MONGER) != 0;
   // such engines run the direct kernels: never binned, no sparse-sharded or exchange state
-  const uint32_t direct_flags = GOSSIP_FLAG_DIRECT | GOSSIP_FLAG_TOPO_PEERS;
+  const uint32_t direct_flags = GOSSIP_FLAG_DIRECT | GOSSIP_FLAG_TOPO_PEERS | GOSSIP_FLAG_MONGER;
   e->fw.D = cfg->stall_rounds;
 
   auto bail = [&](int rc) {
@@ -1538,6 +1559,7 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
   } else if (!alloc(e->img[0], image / 8) || !alloc(e->img[1], image / 8)) {
     return bail(GOSSIP_ENOMEM);
   }
+  if (e->monger && (!alloc(e->hot, shard / 8) || !alloc(e->hot_next, shard / 8))) return bail(GOSSIP_ENOMEM);
   bind_slices(e);
   if (e->mode != GOSSIP_MODE_FLOOD && e->mode != GOSSIP_MODE_ANTIENTROPY && !(cfg->flags & direct_flags) &&
       bin_path_ok(e->N, e->k, e->W, G)) {
@@ -1818,6 +1840,10 @@ int gossip_reset(gossip_engine_t* e) {
     // binned single-shard rounds run in place on S and never read the other image
     HIP_OK(e, hipMemsetAsync(e->S, 0, shard, e->stream));
     if (!e->binned) HIP_OK(e, hipMemsetAsync(e->Snext, 0, shard, e->stream));
+    if (e->monger) {  // (cool and blind stay)
+      HIP_OK(e, hipMemsetAsync(e->hot, 0, shard, e->stream));
+      HIP_OK(e, hipMemsetAsync(e->hot_next, 0, shard, e->stream));
+    }
   }
   if (e->stall_d) HIP_OK(e, hipMemsetAsync(e->stall_d, 0, e->N, e->stream));
   if (e->flood_edges) {
@@ -1864,6 +1890,10 @@ int gossip_inject(gossip_engine_t* e, uint64_t node, uint32_t rumor) {
                                      e->cfg.flags, e->stream));
     return GOSSIP_OK;
   }
+  if (e->monger) {  // hot where it is new; a held rumor, cooled or not, stays as it is
+    HIP_OK(e, launch_monger_inject(e->S, e->hot, e->N, e->R, e->key0, e->key1, (int64_t)node, rumor, e->stream));
+    return GOSSIP_OK;
+  }
   HIP_OK(e, launch_inject(e->S, e->Nl, e->lo, e->hi, e->N, e->R, e->key0, e->key1, (int64_t)node, rumor, e->stream,
                           e->flood_edges ? &e->fw : nullptr));
   e->fr_valid = e->sx_valid = e->gtot_valid = false;
@@ -1888,6 +1918,10 @@ int gossip_inject_random(gossip_engine_t* e) {
   if (e->frontier && e->fr_valid) {
     HIP_OK(e, launch_frontier_inject(e->fb, e->S, e->N, e->partial_d, e->R, e->key0, e->key1, -1, 0, e->cfg.flags,
                                      e->stream));
+    return GOSSIP_OK;
+  }
+  if (e->monger) {
+    HIP_OK(e, launch_monger_inject(e->S, e->hot, e->N, e->R, e->key0, e->key1, -1, 0, e->stream));
     return GOSSIP_OK;
   }
   HIP_OK(e, launch_inject(e->S, e->Nl, e->lo, e->hi, e->N, e->R, e->key0, e->key1, -1, 0, e->stream,
@@ -2577,6 +2611,15 @@ int gossip_ae_finish(gossip_engine_t* e, uint64_t* partial) {
   return GOSSIP_OK;
 }
 
+int gossip_set_monger(gossip_engine_t* e, uint32_t cool, uint32_t blind) {
+  if (!e) return GOSSIP_EINVAL;
+  if (!e->monger) return e->fail(GOSSIP_ESTATE, "gossip_set_monger needs an engine created with GOSSIP_FLAG_MONGER");
+  if (blind > 1) return e->fail(GOSSIP_EINVAL, "blind must be 0 or 1");
+  e->cool = cool;
+  e->blind = blind;
+  return GOSSIP_OK;
+}
+
 int gossip_set_faults(gossip_engine_t* e, uint32_t edge_loss, uint32_t partitions) {
   if (!e) return GOSSIP_EINVAL;
   if ((edge_loss || partitions > 1) && e->mode == GOSSIP_MODE_FLOOD && !e->flood_edges)
@@ -2654,6 +2697,13 @@ int gossip_step(gossip_engine_t* e, uint32_t max_rounds, gossip_round_stats_t* s
     if (infected) std::memcpy(infected + (size_t)r * e->R, part.data() + 4, (size_t)e->R * 8);
     ++r;
     if (rounds_done) *rounds_done = r;
+    // rumor mongering: the traffic after the last delivery is part of the answer,
+    // so the run ends with the first round that sends nothing (reported, as FLOOD's), not at converged.
+    // One round per host read: no round is enqueued ahead, so t and the state are that round's
+    if (e->monger) {
+      if (st.messages == 0) break;
+      continue;
+    }
     // converged, or FLOOD quiescence: no message sent means S_{t+1} == S_t forever
     if (st.converged || (e->mode == GOSSIP_MODE_FLOOD && st.messages == 0)) break;
   }
@@ -2680,6 +2730,17 @@ int gossip_read_shard(gossip_engine_t* e, uint64_t* out, uint64_t n_words) {
   HIP_OK(e, hipStreamSynchronize(e->stream));
   for (uint32_t w = 0; w < e->W; ++w)
     HIP_OK(e, hipMemcpy(out + (size_t)w * e->nown, e->S + (size_t)w * e->Nl, e->nown * 8, hipMemcpyDeviceToHost));
+  return GOSSIP_OK;
+}
+
+int gossip_read_hot_shard(gossip_engine_t* e, uint64_t* out, uint64_t n_words) {
+  if (!e || !out) return GOSSIP_EINVAL;
+  if (!e->monger) return e->fail(GOSSIP_ESTATE, "gossip_read_hot_shard needs an engine created with GOSSIP_FLAG_MONGER");
+  if (n_words < (uint64_t)e->W * e->nown) return e->fail(GOSSIP_EINVAL, "output too small");
+  if (int rc = set_dev(e)) return rc;
+  HIP_OK(e, hipStreamSynchronize(e->stream));
+  for (uint32_t w = 0; w < e->W; ++w)
+    HIP_OK(e, hipMemcpy(out + (size_t)w * e->nown, e->hot + (size_t)w * e->Nl, e->nown * 8, hipMemcpyDeviceToHost));
   return GOSSIP_OK;
 }
 

@@ -18,6 +18,7 @@ FLAG_SHARD_DIRECT = 1 << 4
 FLAG_AE_DIRECT_SCAN = 1 << 5
 FLAG_TOPO_PEERS = 1 << 6  # random modes: peers drawn from the node's topology row
 FLAG_AE_TOPO_PEERS = 1 << 7  # ANTIENTROPY: exchange peers drawn from the node's topology row
+FLAG_MONGER = 1 << 8  # PUSH: rumor mongering, nodes lose interest in what they push
 
 ABI_VERSION = 10  # include/gossip.h GOSSIP_ABI_VERSION (v10: gossip_round_wall)
 
@@ -74,6 +75,7 @@ SIGNATURES = [
     ("inject", C.c_int, [P, C.c_uint64, C.c_uint32]),
     ("inject_random", C.c_int, [P]),
     ("set_faults", C.c_int, [P, C.c_uint32, C.c_uint32]),
+    ("set_monger", C.c_int, [P, C.c_uint32, C.c_uint32]),
     ("set_param", C.c_int, [P, C.c_char_p, C.c_double]),
     ("step", C.c_int, [P, C.c_uint32, C.POINTER(RoundStats), U64P, U32P]),
     ("partial_len", C.c_uint64, [P]),
@@ -115,6 +117,7 @@ SIGNATURES = [
     ("read_bitset", C.c_int, [P, C.c_uint64, U64P, C.c_uint32]),
     ("read_rows", C.c_int, [P, U32P, C.c_uint64]),
     ("read_shard", C.c_int, [P, U64P, C.c_uint64]),
+    ("read_hot_shard", C.c_int, [P, U64P, C.c_uint64]),
     ("read_versions", C.c_int, [P, C.c_uint64, U32P, C.c_uint32, U32P]),
     ("shard_range", C.c_int, [P, U64P, U64P]),
     ("state_hash", C.c_int, [P, U64P]),
@@ -138,7 +141,7 @@ SIGNATURES = [
 ]
 # entry points of the HIP engine only (the oracle library exports the rest under "oracle_")
 ENGINE_ONLY = {"comm_unique_id", "comm_init_rank", "group_create", "group_destroy", "group_engine", "group_transport",
-               "group_step", "group_last_error"}
+               "group_step", "group_last_error", "set_monger", "read_hot_shard"}
 
 
 def bind(lib: C.CDLL, prefix: str, names=None) -> C.CDLL:

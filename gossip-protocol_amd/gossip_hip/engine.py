@@ -467,6 +467,20 @@ class Engine(AbiEngine):
         """This rank's RCCL communicator (gossip_comm_init_rank): gossip_step then runs sharded rounds."""
         self._check(self._fn("comm_init_rank")(self._h, unique_id))
 
+    def set_monger(self, cool, blind: bool = False):
+        """FLAG_MONGER, for the rounds that follow: cool = the chance that a counted
+        contact makes the sender lose interest, a probability (float, turned into x / 2^32 by
+        loss_threshold) or the u32 threshold itself (int); blind: every attempt counts, else feedback."""
+        x = loss_threshold(cool) if isinstance(cool, float) else int(cool)
+        self._check(self._fn("set_monger")(self._h, C.c_uint32(x), C.c_uint32(int(blind))))
+
+    def read_hot(self) -> np.ndarray:
+        """FLAG_MONGER: the rumors each node is still spreading, shaped like read_shard()."""
+        n = self.hi - self.lo
+        out = np.zeros(self.n_words * n, dtype=np.uint64)
+        self._check(self._fn("read_hot_shard")(self._h, out.ctypes.data_as(_abi.U64P), C.c_uint64(out.size)))
+        return out.reshape(self.n_words, n)
+
     def kernel_time(self, which: int):
         ms, n = C.c_double(), C.c_uint64()
         self._check(self._fn("kernel_time")(self._h, C.c_uint32(which), C.byref(ms), C.byref(n)))

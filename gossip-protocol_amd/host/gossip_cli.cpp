@@ -8,6 +8,10 @@
 //              [--topo-peers]   with push-grid, pull-grid or pushpull-grid: random gossip over
 //                               the grid, K of a node's grid neighbours per round
 //                               (GOSSIP_FLAG_TOPO_PEERS); prints the messages sent
+//              [--monger P [--blind]]   with push, or push-grid --topo-peers: rumor mongering
+//                               (GOSSIP_FLAG_MONGER), a counted contact cools the sender with
+//                               probability P (--blind: every attempt counts, else feedback); runs
+//                               to quiescence and prints the residue and the messages per node
 //              [--shards G [--devices d0,d1,...]]   G shards in this process, every round
 //                                                   driven by the library (gossip_group_*:
 //                                                   RCCL over distinct devices, else copies)
@@ -36,7 +40,8 @@ int main(int argc, char** argv) {
   uint32_t rumors = 1, fanout = 3, runs = 3, shards = 1;
   std::vector<int32_t> devices;
   std::string mode = "push";
-  bool hash = false, topo_peers = false;
+  bool hash = false, topo_peers = false, blind = false;
+  double monger = -1.0;  // < 0: off
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
@@ -48,6 +53,8 @@ int main(int argc, char** argv) {
     else if (a == "--runs") runs = (uint32_t)std::strtoul(next(), nullptr, 0);
     else if (a == "--hash") hash = true;
     else if (a == "--topo-peers") topo_peers = true;
+    else if (a == "--monger") monger = std::strtod(next(), nullptr);
+    else if (a == "--blind") blind = true;
     else if (a == "--shards") shards = (uint32_t)std::strtoul(next(), nullptr, 0);
     else if (a == "--devices") {
       for (char* p = next(); *p;) {
@@ -68,7 +75,8 @@ int main(int argc, char** argv) {
   cfg.seed = seed;
   cfg.device = -1;
   cfg.shard_count = 1;
-  cfg.flags = (hash ? GOSSIP_FLAG_HASH : 0) | (topo_peers ? GOSSIP_FLAG_TOPO_PEERS : 0);
+  cfg.flags = (hash ? GOSSIP_FLAG_HASH : 0) | (topo_peers ? GOSSIP_FLAG_TOPO_PEERS : 0) |
+              (monger >= 0 ? GOSSIP_FLAG_MONGER : 0);
   const size_t dash = mode.rfind("-grid");
   const bool grid = dash != std::string::npos && dash + 5 == mode.size();
   const std::string base = grid ? mode.substr(0, dash) : mode;
@@ -78,6 +86,11 @@ int main(int argc, char** argv) {
   }
   if (topo_peers != (grid && base != "flood")) {
     std::fprintf(stderr, "--topo-peers goes with push-grid, pull-grid or pushpull-grid (and they with it)\n");
+    return 2;
+  }
+  if ((monger >= 0 && (base != "push" || shards > 1 || monger > 1.0)) || (blind && monger < 0)) {
+    std::fprintf(stderr, "--monger P (0 <= P <= 1) goes with --mode push or push-grid --topo-peers on one shard, "
+                         "--blind with --monger\n");
     return 2;
   }
   cfg.mode = base == "push" ? GOSSIP_MODE_PUSH : base == "pull" ? GOSSIP_MODE_PULL
@@ -133,6 +146,13 @@ int main(int argc, char** argv) {
       return die(e, "gossip_set_topology_csr", rc);
   }
   std::vector<gossip_round_stats_t> st(4096);
+  std::vector<uint64_t> infected;  // --monger: the per-rumor counts of every round, for the residue
+  if (monger >= 0) {
+    const double x = std::floor(monger * 4294967296.0 + 0.5);
+    if (int rc = gossip_set_monger(e, x >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)x, blind ? 1u : 0u))
+      return die(e, "gossip_set_monger", rc);
+    infected.resize(st.size() * rumors);
+  }
   for (uint32_t run = 0; run < runs; ++run) {
     if (int rc = gossip_reset(e)) return die(e, "gossip_reset", rc);
     if (grid || cfg.mode == GOSSIP_MODE_PUSH || rumors == 1) {
@@ -143,11 +163,28 @@ int main(int argc, char** argv) {
     }
     uint32_t done = 0;
     const auto t0 = std::chrono::steady_clock::now();
-    if (int rc = gossip_step(e, (uint32_t)st.size(), st.data(), nullptr, &done)) return die(e, "gossip_step", rc);
+    if (int rc = gossip_step(e, (uint32_t)st.size(), st.data(), infected.empty() ? nullptr : infected.data(), &done))
+      return die(e, "gossip_step", rc);
     const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     const gossip_round_stats_t& last = st[done ? done - 1 : 0];
     uint64_t messages = 0;  // FLOOD and --topo-peers count them (0 for random gossip over all nodes)
     for (uint32_t r = 0; r < done; ++r) messages += st[r].messages;
+    if (monger >= 0) {  // rounds to quiescence, who never heard each rumor, what it cost
+      uint64_t worst = 0, sum = 0;
+      for (uint32_t r = 0; done && r < rumors; ++r) {
+        const uint64_t miss = nodes - infected[(size_t)(done - 1) * rumors + r];
+        worst = miss > worst ? miss : worst;
+        sum += miss;
+      }
+      std::printf("{\"run\":%u,\"mode\":\"%s\",\"monger\":%.6f,\"blind\":%u,\"nodes\":%llu,\"rumors\":%u,"
+                  "\"rounds\":%u,\"quiescent\":%u,\"converged\":%u,\"residue_max\":%llu,\"residue_mean\":%.3f,"
+                  "\"messages\":%llu,\"messages_per_node\":%.4f,\"seconds\":%.6f,\"state_hash\":\"0x%016llx\"}\n",
+                  run, mode.c_str(), monger, blind ? 1u : 0u, (unsigned long long)nodes, rumors, done,
+                  done && last.messages == 0 ? 1u : 0u, last.converged, (unsigned long long)worst,
+                  (double)sum / rumors, (unsigned long long)messages, (double)messages / (double)nodes, s,
+                  (unsigned long long)last.state_hash);
+      continue;
+    }
     std::printf("{\"run\":%u,\"mode\":\"%s\",\"nodes\":%llu,\"rumors\":%u,\"rounds\":%u,\"converged\":%u,"
                 "\"messages\":%llu,\"node_updates_per_s\":%.4e,\"seconds\":%.6f,\"state_hash\":\"0x%016llx\"}\n",
                 run, mode.c_str(), (unsigned long long)nodes, rumors, done, last.converged,

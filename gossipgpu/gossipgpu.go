@@ -73,6 +73,10 @@ const (
 	// FlagAeTopoPeers: AntiEntropy draws each node's k exchange peers from its topology row by
 	// the same rule (SetTopology first); RoundStats.Messages stays the exchanges that took place.
 	FlagAeTopoPeers Flags = Flags(C.GOSSIP_FLAG_AE_TOPO_PEERS)
+	// FlagMonger: Push as rumor mongering (DESIGN.md §2.13): a node pushes only the rumors it is
+	// still hot on and loses interest by SetMonger's coin; Step runs until a round sends nothing,
+	// and RoundStats.Messages counts k per node that pushed.
+	FlagMonger Flags = Flags(C.GOSSIP_FLAG_MONGER)
 )
 
 // Config mirrors gossip_config_t.  Probabilities are thresholds x / 2^32 (Threshold).
@@ -280,6 +284,19 @@ func (e *Engine) SetFaults(edgeLoss, partitions uint32) error {
 	return e.call(C.gossip_set_faults(e.h, C.uint32_t(edgeLoss), C.uint32_t(partitions)))
 }
 
+// SetMonger sets the cooling rule of an engine created with FlagMonger for the rounds that
+// follow: cool is the chance x / 2^32 (Threshold) that a counted contact makes the sender lose
+// interest; blind counts every attempt, else only delivered pushes whose peer held the rumor.
+func (e *Engine) SetMonger(cool uint32, blind bool) error {
+	e.mu.Lock()
+	defer e.mu.Unlock()
+	b := C.uint32_t(0)
+	if blind {
+		b = 1
+	}
+	return e.call(C.gossip_set_monger(e.h, C.uint32_t(cool), b))
+}
+
 // SetParam sets a tuning / path-selection knob (gossip_set_param); results never change.
 func (e *Engine) SetParam(name string, value float64) error {
 	e.mu.Lock()
@@ -466,6 +483,19 @@ func (e *Engine) ReadShard() ([]uint64, error) {
 	defer e.mu.Unlock()
 	out := make([]uint64, uint64((e.cfg.Rumors+63)/64)*(hi-lo))
 	if rc := C.gossip_read_shard(e.h, u64p(out), C.uint64_t(len(out))); rc != 0 {
+		return nil, e.fail(rc)
+	}
+	return out, nil
+}
+
+// ReadHotShard returns the rumors every owned node is still spreading (FlagMonger), in
+// ReadShard's layout.
+func (e *Engine) ReadHotShard() ([]uint64, error) {
+	lo, hi := e.ShardRange()
+	e.mu.Lock()
+	defer e.mu.Unlock()
+	out := make([]uint64, uint64((e.cfg.Rumors+63)/64)*(hi-lo))
+	if rc := C.gossip_read_hot_shard(e.h, u64p(out), C.uint64_t(len(out))); rc != 0 {
 		return nil, e.fail(rc)
 	}
 	return out, nil

@@ -81,7 +81,7 @@ enum gossip_flags {
                                           Such engines run the direct kernels (as GOSSIP_FLAG_DIRECT),
                                           sharded ones through the state all-gather round.  With FLOOD or
                                           ANTIENTROPY gossip_create returns GOSSIP_EINVAL */
-  GOSSIP_FLAG_AE_TOPO_PEERS = 1u << 7  /* ANTIENTROPY: the k exchanges of node n go to peers drawn from its
+  GOSSIP_FLAG_AE_TOPO_PEERS = 1u << 7, /* ANTIENTROPY: the k exchanges of node n go to peers drawn from its
                                           topology row by the rule of GOSSIP_FLAG_TOPO_PEERS (a sorted set,
                                           self-loops kept, with replacement; an empty row initiates nothing
                                           but still churns, answers and can be picked).
@@ -95,6 +95,22 @@ enum gossip_flags {
                                           direct sparse scan (as "ae_dense_bin" 0 with
                                           GOSSIP_FLAG_AE_DIRECT_SCAN).  With any other mode, or together
                                           with GOSSIP_FLAG_TOPO_PEERS, gossip_create returns GOSSIP_EINVAL */
+  GOSSIP_FLAG_MONGER = 1u << 8         /* PUSH: rumor mongering.  Beside the rumors a node
+                                          knows the engine keeps the ones it is still spreading ("hot",
+                                          gossip_read_hot_shard): a rumor is hot where it is new, a push
+                                          carries only the hot rumors, and a counted contact makes the
+                                          sender lose interest in them with probability cool / 2^32
+                                          (gossip_set_monger: feedback or blind, one coin per edge, Philox
+                                          stream tag 5).  A node with nothing hot initiates nothing;
+                                          stats.messages counts k per initiating node, lost attempts
+                                          included.  gossip_step runs until the first round that sends
+                                          nothing (reported, as FLOOD's), not until converged.  With cool = 0
+                                          (the value after create) the engine equals an unflagged PUSH engine
+                                          bit for bit.  Composes with GOSSIP_FLAG_TOPO_PEERS, _HASH and
+                                          _TIMING and with edge_loss / partitions; such engines run direct
+                                          kernels (as GOSSIP_FLAG_DIRECT; _DIRECT and _DENSE change nothing).
+                                          With any other mode gossip_create returns GOSSIP_EINVAL, with
+                                          stall_rounds or shard_count > 1 GOSSIP_ENOTSUP */
 };
 
 typedef struct gossip_config {
@@ -143,8 +159,10 @@ typedef struct gossip_round_stats {
                            GOSSIP_FLAG_AE_TOPO_PEERS too: completed exchanges, not attempts);
                            GOSSIP_FLAG_TOPO_PEERS: exchanges initiated in round t, lost attempts
                            included — k per node with a row that is not empty
-                           and not stalled (PUSH: and a rumor to send); other random-mode
-                           engines: 0                                               */
+                           and not stalled (PUSH: and a rumor to send);
+                           GOSSIP_FLAG_MONGER: k per node that holds a hot rumor (and, with
+                           GOSSIP_FLAG_TOPO_PEERS, has a row), lost attempts included
+                           (DESIGN.md §2.13); other random-mode engines: 0           */
   uint64_t state_hash;  /* GOSSIP_FLAG_HASH: Σ mix64 over nonzero words, else 0   */
 } gossip_round_stats_t;
 
@@ -237,11 +255,13 @@ int gossip_set_param(gossip_engine_t* eng, const char* name, double value);
 int gossip_set_topology_csr(gossip_engine_t* eng, const uint32_t* row_ptr, const uint32_t* col,
                             uint64_t n, uint64_t n_edges);
 
-/* Clears every rumor bit and sets t = 0. */
+/* Clears every rumor bit (GOSSIP_FLAG_MONGER: the hot bits too; cool and blind stay) and sets t = 0. */
 int gossip_reset(gossip_engine_t* eng);
 
 /* Client broadcast of rumor slot `rumor` to `node` (no-op when the node is
  * outside this shard or already holds it — the dedupe of main.go:113).
+ * GOSSIP_FLAG_MONGER: the rumor is hot at a node it is new at; one the node holds
+ * already, cooled or not, stays as it is (gossip_inject_random likewise).
  * ANTIENTROPY: a local write of key `rumor` at `node` (its version + 1). */
 int gossip_inject(gossip_engine_t* eng, uint64_t node, uint32_t rumor);
 
@@ -256,8 +276,17 @@ int gossip_inject_random(gossip_engine_t* eng);
  * round index stay.  Sharded engines: set the same values on every rank. */
 int gossip_set_faults(gossip_engine_t* eng, uint32_t edge_loss, uint32_t partitions);
 
+/* GOSSIP_FLAG_MONGER, for the rounds that follow: cool = P(a counted contact makes
+ * the sender lose interest) as x / 2^32; blind = 0: feedback, a delivered push counts the rumors the
+ * peer already held and a lost one counts nothing; blind = 1: every attempt counts every hot rumor,
+ * delivered or lost.  After create cool = 0 and blind = 0; gossip_reset keeps both.  GOSSIP_ESTATE on
+ * an engine created without the flag, GOSSIP_EINVAL for blind > 1. */
+int gossip_set_monger(gossip_engine_t* eng, uint32_t cool, uint32_t blind);
+
 /* Runs rounds until converged (FLOOD also: a round that sends nothing) or max_rounds
- * rounds have run.  stats: max_rounds entries or NULL; infected: max_rounds * R
+ * rounds have run.  GOSSIP_FLAG_MONGER: until the first round that sends nothing (that round is
+ * reported) or max_rounds, and not until converged; on return gossip_round_index and the state
+ * are those of the last reported round.  stats: max_rounds entries or NULL; infected: max_rounds * R
  * counters (row t = per-rumor infected counts after round t) or NULL.
  * G > 1: the engine needs its collectives first (gossip_comm_init_rank below); every
  * rank calls gossip_step with the same max_rounds and gets the same global stats. */
@@ -302,6 +331,9 @@ const char* gossip_group_last_error(const gossip_group_t* grp);
  * or the whole owned shard in logical order out[w * Nl_owned + i]. */
 int gossip_read_bitset(gossip_engine_t* eng, uint64_t node, uint64_t* out, uint32_t nwords);
 int gossip_read_shard(gossip_engine_t* eng, uint64_t* out, uint64_t n_words);
+/* GOSSIP_FLAG_MONGER: the rumors every node is still hot on, in the layout of gossip_read_shard (a
+ * subset of it); GOSSIP_ESTATE on an engine created without the flag. */
+int gossip_read_hot_shard(gossip_engine_t* eng, uint64_t* out, uint64_t n_words);
 /* ANTIENTROPY readout: the K versions of one node (owned by this shard), and its alive flag. */
 int gossip_read_versions(gossip_engine_t* eng, uint64_t node, uint32_t* out, uint32_t ncomp, uint32_t* alive);
 /* ANTIENTROPY readout of every owned row: out[i * K + c] for owned node lo + i. */
