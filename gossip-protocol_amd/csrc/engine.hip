@@ -105,6 +105,9 @@ struct gossip_engine {
   bool monger = false;
   uint32_t cool = 0, blind = 0;  // gossip_set_monger
   DevBuf<uint64_t> hot, hot_next;
+  // counters: four bit planes [4][W][N], held from the first limit above 1 on
+  uint32_t limit = 1;  // gossip_set_monger_limit
+  DevBuf<uint64_t> counts;
   // stall mode, random modes: streak per node, all N nodes on every shard
   DevBuf<uint8_t> stall_d;
   // FLOOD with faults, one shard: per out-edge pending values and first senders
@@ -1224,7 +1227,9 @@ int compute_round(gossip_engine* e, const uint64_t* gathered) {
     HIP_OK(e, hipMemcpyAsync(e->Snext, e->S, bytes, hipMemcpyDeviceToDevice, e->stream));
     if (e->monger) {  // rumor mongering: H moves with S
       HIP_OK(e, hipMemcpyAsync(e->hot_next, e->hot, bytes, hipMemcpyDeviceToDevice, e->stream));
-      HIP_OK(e, launch_round_monger(MongerArgs{a, e->hot, e->hot_next, e->cool, e->blind, e->topo_peers}, e->stream));
+      const MongerArgs m{a, e->hot, e->hot_next, e->cool, e->blind, e->topo_peers};
+      if (e->counts) HIP_OK(e, launch_round_monger_count(MongerCountArgs{m, e->counts, e->limit}, e->stream));  // §2.14
+      else HIP_OK(e, launch_round_monger(m, e->stream));
     } else if (e->topo_peers) {
       HIP_OK(e, launch_round_topo(a, e->stream));  // peers from the rows
     } else {
@@ -1843,6 +1848,7 @@ int gossip_reset(gossip_engine_t* e) {
     if (e->monger) {  // (cool and blind stay)
       HIP_OK(e, hipMemsetAsync(e->hot, 0, shard, e->stream));
       HIP_OK(e, hipMemsetAsync(e->hot_next, 0, shard, e->stream));
+      if (e->counts) HIP_OK(e, hipMemsetAsync(e->counts, 0, 4 * shard, e->stream));  // (the limit stays)
     }
   }
   if (e->stall_d) HIP_OK(e, hipMemsetAsync(e->stall_d, 0, e->N, e->stream));
@@ -2620,6 +2626,24 @@ int gossip_set_monger(gossip_engine_t* e, uint32_t cool, uint32_t blind) {
   return GOSSIP_OK;
 }
 
+int gossip_set_monger_limit(gossip_engine_t* e, uint32_t limit) {
+  if (!e) return GOSSIP_EINVAL;
+  if (!e->monger)
+    return e->fail(GOSSIP_ESTATE, "gossip_set_monger_limit needs an engine created with GOSSIP_FLAG_MONGER");
+  if (limit < 1 || limit > 15) return e->fail(GOSSIP_EINVAL, "limit must be in [1, 15]");
+  if (limit > 1 && !e->counts) {  // counts are kept from here on: what cooled before reads 0
+    if (int rc = set_dev(e)) return rc;
+    const size_t n = (size_t)4 * e->W * e->Nl;
+    DevBuf<uint64_t> planes;
+    if (planes.alloc(n, false) != hipSuccess)
+      return e->fail(GOSSIP_ENOMEM, "hipMalloc of %zu bytes for the counters failed", n * 8);
+    HIP_OK(e, hipMemsetAsync(planes, 0, n * 8, e->stream));
+    e->counts = std::move(planes);
+  }
+  e->limit = limit;
+  return GOSSIP_OK;
+}
+
 int gossip_set_faults(gossip_engine_t* e, uint32_t edge_loss, uint32_t partitions) {
   if (!e) return GOSSIP_EINVAL;
   if ((edge_loss || partitions > 1) && e->mode == GOSSIP_MODE_FLOOD && !e->flood_edges)
@@ -2741,6 +2765,25 @@ int gossip_read_hot_shard(gossip_engine_t* e, uint64_t* out, uint64_t n_words) {
   HIP_OK(e, hipStreamSynchronize(e->stream));
   for (uint32_t w = 0; w < e->W; ++w)
     HIP_OK(e, hipMemcpy(out + (size_t)w * e->nown, e->hot + (size_t)w * e->Nl, e->nown * 8, hipMemcpyDeviceToHost));
+  return GOSSIP_OK;
+}
+
+int gossip_read_monger_counts(gossip_engine_t* e, uint64_t* out, uint64_t n_words) {
+  if (!e || !out) return GOSSIP_EINVAL;
+  if (!e->monger)
+    return e->fail(GOSSIP_ESTATE, "gossip_read_monger_counts needs an engine created with GOSSIP_FLAG_MONGER");
+  const uint64_t plane = (uint64_t)e->W * e->nown;
+  if (n_words != 4 * plane) return e->fail(GOSSIP_EINVAL, "n_words must be 4 * W * Nl_owned");
+  if (!e->counts) {  // no limit above 1 yet: nothing was counted
+    std::memset(out, 0, n_words * 8);
+    return GOSSIP_OK;
+  }
+  if (int rc = set_dev(e)) return rc;
+  HIP_OK(e, hipStreamSynchronize(e->stream));
+  for (uint32_t b = 0; b < 4; ++b)
+    for (uint32_t w = 0; w < e->W; ++w)
+      HIP_OK(e, hipMemcpy(out + b * plane + (size_t)w * e->nown, e->counts + ((size_t)b * e->W + w) * e->Nl,
+                          e->nown * 8, hipMemcpyDeviceToHost));
   return GOSSIP_OK;
 }
 

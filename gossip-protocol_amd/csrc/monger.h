@@ -2,6 +2,9 @@
 // An engine created with GOSSIP_FLAG_MONGER keeps, beside S (the rumors a node knows), a second
 // bitset H ⊆ S per node in the same layout (the rumors it is still spreading, "hot").  A push
 // carries only the hot rumors; a counted contact cools them with probability cool / 2^32.
+// From the first gossip_set_monger_limit above 1 on the engine also keeps a count in 0..15 per node
+// and rumor: a contact whose coin holds is counted, and a rumor cools
+// once its count reaches the limit.
 //
 // Reference: (*NodeState).Gossip forwards every value once (main.go:65-89) and the broadcast
 // handler drops a value it holds (main.go:113); rumor mongering (Demers et al., "Epidemic
@@ -26,6 +29,14 @@ struct MongerArgs {
   bool topo;           // peers drawn from the rows (GOSSIP_FLAG_TOPO_PEERS) or from all N nodes
 };
 
+// The round with counters: bit r of plane b of C[n][r] at
+// C[(b * W + w) * N + n], r = 64 w + bit.  Only lane n reads or writes C[*][n].
+struct MongerCountArgs {
+  MongerArgs m;
+  uint64_t* C;     // [4][W][N], updated in place
+  uint32_t limit;  // 1..15: a rumor cools at a counted contact that leaves its count at or above this
+};
+
 // The cooling coins of edges 4q .. 4q + 3 of node n in round t: Philox stream tag 5.
 __host__ __device__ __forceinline__ u32x4 cool_draws(uint32_t n, uint32_t t, uint32_t q, uint32_t k0, uint32_t k1) {
   return philox4x32_10(u32x4{n, t, 5u, q}, k0, k1);
@@ -34,6 +45,9 @@ __host__ __device__ __forceinline__ u32x4 cool_draws(uint32_t n, uint32_t t, uin
 // One round: ORs the pushes into a.Snext and Hnext, clears the cooled bits of Hnext, and adds k per
 // initiating node to a.partial[2].
 hipError_t launch_round_monger(const MongerArgs& m, hipStream_t st);
+// The same round for an engine that holds counters: a coin that holds adds one to the count of every
+// rumor of its counted set (saturating at 15), and a rumor cools when that leaves it at c.limit or more.
+hipError_t launch_round_monger_count(const MongerCountArgs& c, hipStream_t st);
 // Client broadcast: node >= 0 sets one bit, node < 0 every rumor at its tag-2 origin; the bit is
 // set in H only where it is new in S (a cooled rumor is not re-heated).
 hipError_t launch_monger_inject(uint64_t* S, uint64_t* H, uint64_t N, uint32_t R, uint32_t key0, uint32_t key1,

@@ -15,6 +15,9 @@
 //
 // blind is a run-time value, not a template parameter: the gather of S_t[p] decides which bits
 // are new at p (and so hot there) in both variants, so a blind kernel would save no load.
+//
+// An engine that holds counters (gossip_set_monger_limit above 1) runs the sibling
+// round_monger_count_kernel; every other engine launches round_monger_kernel as before.
 #include "monger.h"
 
 #include "topo_peers.h"
@@ -145,6 +148,140 @@ __global__ __launch_bounds__(kBlock) void round_monger_kernel(MongerArgs m) {
   if ((threadIdx.x & 63) == 0 && msgs) atomicAdd((unsigned long long*)&a.partial[2], (unsigned long long)msgs);
 }
 
+// ---------------------------------------------------------------------------
+// The round with counters: C[n][r] in 0..15 as four bit planes in the
+// layout of S and H, so that one instruction updates 64 rumors.  Only lane n touches C[*][n]: plain
+// loads and stores.  The planes of a word are loaded before the batch's atomics are issued and are
+// consumed before them, as every other load of the batch.
+// ---------------------------------------------------------------------------
+
+// c += 1 at the bits of x, saturating at 15: a ripple-carry add over the planes; a carry out of
+// plane 3 sets all four planes of those bits.
+__device__ __forceinline__ void planes_add(uint64_t (&c)[4], uint64_t x) {
+  uint64_t carry = x;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const uint64_t t = c[b] & carry;
+    c[b] ^= carry;
+    carry = t;
+  }
+#pragma unroll
+  for (int b = 0; b < 4; ++b) c[b] |= carry;
+}
+
+// The bits whose count is at least limit (uniform, 1..15), most significant plane first.
+__device__ __forceinline__ uint64_t planes_ge(const uint64_t (&c)[4], uint32_t limit) {
+  uint64_t gt = 0, eq = ~0ull;
+#pragma unroll
+  for (int b = 3; b >= 0; --b) {
+    if ((limit >> b) & 1u) {
+      eq &= c[b];
+    } else {
+      gt |= eq & c[b];
+      eq &= ~c[b];
+    }
+  }
+  return gt | eq;
+}
+
+// What one batch does to one word of a counting engine: push_word, but an edge whose coin holds adds
+// its counted set to the planes c (in registers).  Returns the bits that were incremented.
+__device__ __forceinline__ uint64_t count_word(const MongerArgs& m, uint64_t h, uint64_t woff, const uint32_t (&p)[4],
+                                               const bool (&live)[4], const bool (&coin)[4], uint64_t (&c)[4]) {
+  const RoundArgs& a = m.a;
+  uint64_t pv[4], nb[4], x[4], inc = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) pv[i] = live[i] ? a.G[woff + p[i]] : 0ull;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    nb[i] = live[i] ? (h & ~pv[i]) : 0ull;
+    const uint64_t counted = m.blind ? h : (live[i] ? (h & pv[i]) : 0ull);
+    x[i] = coin[i] ? counted : 0ull;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (x[i]) {
+      planes_add(c, x[i]);
+      inc |= x[i];
+    }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (nb[i]) {
+      atomicOr((unsigned long long*)&a.Snext[woff + p[i]], (unsigned long long)nb[i]);
+      atomicOr((unsigned long long*)&m.Hnext[woff + p[i]], (unsigned long long)nb[i]);
+    }
+  return inc;
+}
+
+// Ends a word (one word: after every batch; several: after each): the incremented rumors whose count
+// has reached the limit cool, and the planes go back only when something was counted.  Cooling per
+// batch equals cooling per round: counts only grow within a round, and
+// the last batch that increments a rumor sees its final count.
+__device__ __forceinline__ void count_close(const MongerCountArgs& ca, uint64_t at, uint64_t plane, uint64_t inc,
+                                            const uint64_t (&c)[4]) {
+  if (inc == 0) return;
+  const uint64_t clear = planes_ge(c, ca.limit) & inc;
+  if (clear) atomicAnd((unsigned long long*)&ca.m.Hnext[at], (unsigned long long)~clear);
+#pragma unroll
+  for (int b = 0; b < 4; ++b) ca.C[(uint64_t)b * plane + at] = c[b];
+}
+
+template <bool ONE_WORD, bool TOPO, bool FAULTS>
+__global__ __launch_bounds__(kBlock) void round_monger_count_kernel(MongerCountArgs ca) {
+  const MongerArgs& m = ca.m;
+  const RoundArgs& a = m.a;
+  uint64_t msgs = 0;
+  const uint32_t nblk = (a.k + 3u) >> 2;
+  const uint64_t plane = (uint64_t)a.W * a.N;
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t s = (uint64_t)blockIdx.x * kBlock + threadIdx.x; s < a.N; s += stride) {
+    const uint32_t n = (uint32_t)s;
+    uint64_t h = 0;
+    if (ONE_WORD) {
+      h = m.H[s];
+    } else {
+      for (uint32_t w = 0; w < a.W; ++w) h |= m.H[(uint64_t)w * a.N + s];
+    }
+    if (h == 0) continue;  // nothing hot: no push, no message, and no plane is read
+    uint32_t b = 0, d = 0;
+    if (TOPO) {
+      b = a.orow[n];
+      d = a.orow[n + 1] - b;
+      if (d == 0) continue;
+    }
+    msgs += a.k;
+    const Reach rc = FAULTS ? reach_of(n, a.fa) : Reach{0u, 0xFFFFFFFFu};
+    uint32_t p[4];
+    bool live[4], coin[4];
+    uint64_t c[4];
+    if (ONE_WORD) {  // the planes stay in registers across the batches
+#pragma unroll
+      for (int i = 0; i < 4; ++i) c[i] = ca.C[(uint64_t)i * plane + s];
+      uint64_t inc = 0;
+      for (uint32_t q = 0; q < nblk; ++q) {
+        resolve_batch<TOPO, FAULTS>(m, rc, n, b, d, q, min(4u, a.k - 4u * q), p, live, coin);
+        inc |= count_word(m, h, 0, p, live, coin, c);
+      }
+      count_close(ca, s, plane, inc, c);
+    } else {  // per word and batch, as the AND of round_monger_kernel
+      for (uint32_t q = 0; q < nblk; ++q) {
+        resolve_batch<TOPO, FAULTS>(m, rc, n, b, d, q, min(4u, a.k - 4u * q), p, live, coin);
+        for (uint32_t w = 0; w < a.W; ++w) {
+          const uint64_t woff = (uint64_t)w * a.N;
+          const uint64_t hw = m.H[woff + s];
+          if (hw == 0) continue;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) c[i] = ca.C[(uint64_t)i * plane + woff + s];
+          const uint64_t inc = count_word(m, hw, woff, p, live, coin, c);
+          count_close(ca, woff + s, plane, inc, c);
+        }
+      }
+    }
+  }
+  msgs = wave_sum_u64(msgs);
+  if ((threadIdx.x & 63) == 0 && msgs) atomicAdd((unsigned long long*)&a.partial[2], (unsigned long long)msgs);
+}
+
 __global__ void monger_inject_kernel(uint64_t* S, uint64_t* H, uint64_t N, uint32_t R, uint32_t key0, uint32_t key1,
                                      int64_t node, uint32_t rumor) {
   const uint32_t r = node >= 0 ? rumor : blockIdx.x * blockDim.x + threadIdx.x;
@@ -169,7 +306,25 @@ void launch_faults(const MongerArgs& m, uint32_t grid, hipStream_t st) {
   else round_monger_kernel<ONE_WORD, TOPO, false><<<grid, kBlock, 0, st>>>(m);
 }
 
+template <bool ONE_WORD, bool TOPO>
+void launch_count_faults(const MongerCountArgs& c, uint32_t grid, hipStream_t st) {
+  if (c.m.a.fa.any()) round_monger_count_kernel<ONE_WORD, TOPO, true><<<grid, kBlock, 0, st>>>(c);
+  else round_monger_count_kernel<ONE_WORD, TOPO, false><<<grid, kBlock, 0, st>>>(c);
+}
+
 }  // namespace
+
+hipError_t launch_round_monger_count(const MongerCountArgs& c, hipStream_t st) {
+  const uint32_t grid = grid_for(c.m.a.N);
+  if (c.m.a.W == 1) {
+    if (c.m.topo) launch_count_faults<true, true>(c, grid, st);
+    else launch_count_faults<true, false>(c, grid, st);
+  } else {
+    if (c.m.topo) launch_count_faults<false, true>(c, grid, st);
+    else launch_count_faults<false, false>(c, grid, st);
+  }
+  return hipGetLastError();
+}
 
 hipError_t launch_round_monger(const MongerArgs& m, hipStream_t st) {
   const uint32_t grid = grid_for(m.a.N);

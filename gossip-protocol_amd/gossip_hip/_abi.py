@@ -76,6 +76,7 @@ SIGNATURES = [
     ("inject_random", C.c_int, [P]),
     ("set_faults", C.c_int, [P, C.c_uint32, C.c_uint32]),
     ("set_monger", C.c_int, [P, C.c_uint32, C.c_uint32]),
+    ("set_monger_limit", C.c_int, [P, C.c_uint32]),
     ("set_param", C.c_int, [P, C.c_char_p, C.c_double]),
     ("step", C.c_int, [P, C.c_uint32, C.POINTER(RoundStats), U64P, U32P]),
     ("partial_len", C.c_uint64, [P]),
@@ -118,6 +119,7 @@ SIGNATURES = [
     ("read_rows", C.c_int, [P, U32P, C.c_uint64]),
     ("read_shard", C.c_int, [P, U64P, C.c_uint64]),
     ("read_hot_shard", C.c_int, [P, U64P, C.c_uint64]),
+    ("read_monger_counts", C.c_int, [P, U64P, C.c_uint64]),
     ("read_versions", C.c_int, [P, C.c_uint64, U32P, C.c_uint32, U32P]),
     ("shard_range", C.c_int, [P, U64P, U64P]),
     ("state_hash", C.c_int, [P, U64P]),
@@ -141,7 +143,8 @@ SIGNATURES = [
 ]
 # entry points of the HIP engine only (the oracle library exports the rest under "oracle_")
 ENGINE_ONLY = {"comm_unique_id", "comm_init_rank", "group_create", "group_destroy", "group_engine", "group_transport",
-               "group_step", "group_last_error", "set_monger", "read_hot_shard"}
+               "group_step", "group_last_error", "set_monger", "read_hot_shard", "set_monger_limit",
+               "read_monger_counts"}
 
 
 def bind(lib: C.CDLL, prefix: str, names=None) -> C.CDLL:

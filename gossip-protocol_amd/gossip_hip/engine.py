@@ -481,6 +481,25 @@ class Engine(AbiEngine):
         self._check(self._fn("read_hot_shard")(self._h, out.ctypes.data_as(_abi.U64P), C.c_uint64(out.size)))
         return out.reshape(self.n_words, n)
 
+    def set_monger_limit(self, limit: int):
+        """FLAG_MONGER with counters, for the rounds that follow: a rumor cools only
+        once `limit` (1..15) of its counted contacts have passed set_monger's coin; 1, the value after
+        create, is the coin alone.  Counts are kept from the first limit above 1 on."""
+        self._check(self._fn("set_monger_limit")(self._h, C.c_uint32(int(limit))))
+
+    def read_counts(self) -> np.ndarray:
+        """FLAG_MONGER: the count of every owned node and rumor, uint8 [n_rumors, n] (zeros while no
+        limit above 1 was set), unpacked from gossip_read_monger_counts' four bit planes."""
+        n = self.hi - self.lo
+        planes = np.zeros(4 * self.n_words * n, dtype=np.uint64)
+        self._check(self._fn("read_monger_counts")(self._h, planes.ctypes.data_as(_abi.U64P), C.c_uint64(planes.size)))
+        planes = planes.reshape(4, self.n_words, n)
+        out = np.zeros((self.n_rumors, n), dtype=np.uint8)
+        for r in range(self.n_rumors):
+            for b in range(4):
+                out[r] |= ((planes[b, r // 64] >> np.uint64(r % 64)) & np.uint64(1)).astype(np.uint8) << b
+        return out
+
     def kernel_time(self, which: int):
         ms, n = C.c_double(), C.c_uint64()
         self._check(self._fn("kernel_time")(self._h, C.c_uint32(which), C.byref(ms), C.byref(n)))

@@ -12,6 +12,9 @@
 //                               (GOSSIP_FLAG_MONGER), a counted contact cools the sender with
 //                               probability P (--blind: every attempt counts, else feedback); runs
 //                               to quiescence and prints the residue and the messages per node
+//              [--monger-limit M]   with --monger: the counter rule (gossip_set_monger_limit), a
+//                               rumor cools once M (1..15) counted contacts have passed the coin;
+//                               the paper's pure counter is --monger 1 --monger-limit M
 //              [--shards G [--devices d0,d1,...]]   G shards in this process, every round
 //                                                   driven by the library (gossip_group_*:
 //                                                   RCCL over distinct devices, else copies)
@@ -42,6 +45,8 @@ int main(int argc, char** argv) {
   std::string mode = "push";
   bool hash = false, topo_peers = false, blind = false;
   double monger = -1.0;  // < 0: off
+  uint32_t monger_limit = 1;
+  bool limit_given = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
@@ -55,6 +60,10 @@ int main(int argc, char** argv) {
     else if (a == "--topo-peers") topo_peers = true;
     else if (a == "--monger") monger = std::strtod(next(), nullptr);
     else if (a == "--blind") blind = true;
+    else if (a == "--monger-limit") {
+      monger_limit = (uint32_t)std::strtoul(next(), nullptr, 0);
+      limit_given = true;
+    }
     else if (a == "--shards") shards = (uint32_t)std::strtoul(next(), nullptr, 0);
     else if (a == "--devices") {
       for (char* p = next(); *p;) {
@@ -91,6 +100,10 @@ int main(int argc, char** argv) {
   if ((monger >= 0 && (base != "push" || shards > 1 || monger > 1.0)) || (blind && monger < 0)) {
     std::fprintf(stderr, "--monger P (0 <= P <= 1) goes with --mode push or push-grid --topo-peers on one shard, "
                          "--blind with --monger\n");
+    return 2;
+  }
+  if (limit_given && (monger < 0 || monger_limit < 1 || monger_limit > 15)) {
+    std::fprintf(stderr, "--monger-limit M (1 <= M <= 15) goes with --monger\n");
     return 2;
   }
   cfg.mode = base == "push" ? GOSSIP_MODE_PUSH : base == "pull" ? GOSSIP_MODE_PULL
@@ -151,6 +164,8 @@ int main(int argc, char** argv) {
     const double x = std::floor(monger * 4294967296.0 + 0.5);
     if (int rc = gossip_set_monger(e, x >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)x, blind ? 1u : 0u))
       return die(e, "gossip_set_monger", rc);
+    if (limit_given)
+      if (int rc = gossip_set_monger_limit(e, monger_limit)) return die(e, "gossip_set_monger_limit", rc);
     infected.resize(st.size() * rumors);
   }
   for (uint32_t run = 0; run < runs; ++run) {
@@ -176,10 +191,11 @@ int main(int argc, char** argv) {
         worst = miss > worst ? miss : worst;
         sum += miss;
       }
-      std::printf("{\"run\":%u,\"mode\":\"%s\",\"monger\":%.6f,\"blind\":%u,\"nodes\":%llu,\"rumors\":%u,"
+      std::printf("{\"run\":%u,\"mode\":\"%s\",\"monger\":%.6f,\"blind\":%u,\"monger_limit\":%u,\"nodes\":%llu,"
+                  "\"rumors\":%u,"
                   "\"rounds\":%u,\"quiescent\":%u,\"converged\":%u,\"residue_max\":%llu,\"residue_mean\":%.3f,"
                   "\"messages\":%llu,\"messages_per_node\":%.4f,\"seconds\":%.6f,\"state_hash\":\"0x%016llx\"}\n",
-                  run, mode.c_str(), monger, blind ? 1u : 0u, (unsigned long long)nodes, rumors, done,
+                  run, mode.c_str(), monger, blind ? 1u : 0u, monger_limit, (unsigned long long)nodes, rumors, done,
                   done && last.messages == 0 ? 1u : 0u, last.converged, (unsigned long long)worst,
                   (double)sum / rumors, (unsigned long long)messages, (double)messages / (double)nodes, s,
                   (unsigned long long)last.state_hash);

@@ -297,6 +297,16 @@ func (e *Engine) SetMonger(cool uint32, blind bool) error {
 	return e.call(C.gossip_set_monger(e.h, C.uint32_t(cool), b))
 }
 
+// SetMongerLimit adds the counter rule to an engine created with FlagMonger, for the rounds that
+// follow (DESIGN.md §2.14): a rumor cools only once limit (1..15) of its counted contacts have
+// passed SetMonger's coin.  1, the value after New, is the coin alone; the pure counter is
+// SetMonger(math.MaxUint32, blind) with SetMongerLimit(m).
+func (e *Engine) SetMongerLimit(limit uint32) error {
+	e.mu.Lock()
+	defer e.mu.Unlock()
+	return e.call(C.gossip_set_monger_limit(e.h, C.uint32_t(limit)))
+}
+
 // SetParam sets a tuning / path-selection knob (gossip_set_param); results never change.
 func (e *Engine) SetParam(name string, value float64) error {
 	e.mu.Lock()
@@ -496,6 +506,20 @@ func (e *Engine) ReadHotShard() ([]uint64, error) {
 	defer e.mu.Unlock()
 	out := make([]uint64, uint64((e.cfg.Rumors+63)/64)*(hi-lo))
 	if rc := C.gossip_read_hot_shard(e.h, u64p(out), C.uint64_t(len(out))); rc != 0 {
+		return nil, e.fail(rc)
+	}
+	return out, nil
+}
+
+// ReadMongerCounts returns the counts of SetMongerLimit (FlagMonger) as four bit planes, each in
+// ReadShard's layout: bit b of a count is in out[(b*W+w)*owned+i].  All zero while no limit
+// above 1 was set.
+func (e *Engine) ReadMongerCounts() ([]uint64, error) {
+	lo, hi := e.ShardRange()
+	e.mu.Lock()
+	defer e.mu.Unlock()
+	out := make([]uint64, 4*uint64((e.cfg.Rumors+63)/64)*(hi-lo))
+	if rc := C.gossip_read_monger_counts(e.h, u64p(out), C.uint64_t(len(out))); rc != 0 {
 		return nil, e.fail(rc)
 	}
 	return out, nil

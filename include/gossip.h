@@ -110,7 +110,10 @@ enum gossip_flags {
                                           _TIMING and with edge_loss / partitions; such engines run direct
                                           kernels (as GOSSIP_FLAG_DIRECT; _DIRECT and _DENSE change nothing).
                                           With any other mode gossip_create returns GOSSIP_EINVAL, with
-                                          stall_rounds or shard_count > 1 GOSSIP_ENOTSUP */
+                                          stall_rounds or shard_count > 1 GOSSIP_ENOTSUP.
+                                          gossip_set_monger_limit adds the counter rule:
+                                          a rumor cools only once `limit` of its counted contacts have
+                                          passed the coin; the counts are read by gossip_read_monger_counts */
 };
 
 typedef struct gossip_config {
@@ -255,13 +258,14 @@ int gossip_set_param(gossip_engine_t* eng, const char* name, double value);
 int gossip_set_topology_csr(gossip_engine_t* eng, const uint32_t* row_ptr, const uint32_t* col,
                             uint64_t n, uint64_t n_edges);
 
-/* Clears every rumor bit (GOSSIP_FLAG_MONGER: the hot bits too; cool and blind stay) and sets t = 0. */
+/* Clears every rumor bit (GOSSIP_FLAG_MONGER: the hot bits and the counts too; cool, blind and the
+ * limit stay) and sets t = 0. */
 int gossip_reset(gossip_engine_t* eng);
 
 /* Client broadcast of rumor slot `rumor` to `node` (no-op when the node is
  * outside this shard or already holds it — the dedupe of main.go:113).
  * GOSSIP_FLAG_MONGER: the rumor is hot at a node it is new at; one the node holds
- * already, cooled or not, stays as it is (gossip_inject_random likewise).
+ * already, cooled or not, stays as it is, and so does its count (gossip_inject_random likewise).
  * ANTIENTROPY: a local write of key `rumor` at `node` (its version + 1). */
 int gossip_inject(gossip_engine_t* eng, uint64_t node, uint32_t rumor);
 
@@ -280,8 +284,22 @@ int gossip_set_faults(gossip_engine_t* eng, uint32_t edge_loss, uint32_t partiti
  * the sender lose interest) as x / 2^32; blind = 0: feedback, a delivered push counts the rumors the
  * peer already held and a lost one counts nothing; blind = 1: every attempt counts every hot rumor,
  * delivered or lost.  After create cool = 0 and blind = 0; gossip_reset keeps both.  GOSSIP_ESTATE on
- * an engine created without the flag, GOSSIP_EINVAL for blind > 1. */
+ * an engine created without the flag, GOSSIP_EINVAL for blind > 1.  A counted contact whose coin holds
+ * cools at once while the limit is 1 (the value after create), else it is counted first:
+ * gossip_set_monger_limit. */
 int gossip_set_monger(gossip_engine_t* eng, uint32_t cool, uint32_t blind);
+
+/* GOSSIP_FLAG_MONGER with counters, for the rounds that follow: limit in 1..15.  Every
+ * node keeps a count in 0..15 per rumor; each edge whose coin holds adds one to the count of every rumor
+ * of its counted set (saturating at 15), and a rumor cools at the node iff the round added to its count
+ * and the count is then at least `limit`.  limit = 1 is gossip_set_monger's rule itself; Demers et
+ * al.'s pure counter is cool = 2^32 - 1 (a coin that fails with probability 2^-32) with limit = m.  After
+ * create the limit is 1; gossip_reset keeps it and clears the counts.  Counts are kept from the first
+ * call with limit > 1 on (that call allocates them, zeroed: a rumor that cooled earlier reads 0), also
+ * after the limit is set back to 1; a lowered limit cools a hot rumor at its next counted contact whose
+ * coin holds, not before.  GOSSIP_ESTATE on an engine created without the flag, GOSSIP_EINVAL for 0 or
+ * more than 15, GOSSIP_ENOMEM when the counts cannot be allocated (engine and limit then unchanged). */
+int gossip_set_monger_limit(gossip_engine_t* eng, uint32_t limit);
 
 /* Runs rounds until converged (FLOOD also: a round that sends nothing) or max_rounds
  * rounds have run.  GOSSIP_FLAG_MONGER: until the first round that sends nothing (that round is
@@ -334,6 +352,11 @@ int gossip_read_shard(gossip_engine_t* eng, uint64_t* out, uint64_t n_words);
 /* GOSSIP_FLAG_MONGER: the rumors every node is still hot on, in the layout of gossip_read_shard (a
  * subset of it); GOSSIP_ESTATE on an engine created without the flag. */
 int gossip_read_hot_shard(gossip_engine_t* eng, uint64_t* out, uint64_t n_words);
+/* GOSSIP_FLAG_MONGER: the counts of gossip_set_monger_limit as four bit planes in the layout of
+ * gossip_read_shard, bit b of the count of rumor 64 w + j at node lo + i = bit j of
+ * out[(b * W + w) * Nl_owned + i]; n_words must be 4 * W * Nl_owned (else GOSSIP_EINVAL).  All zero
+ * while no limit above 1 was ever set.  GOSSIP_ESTATE on an engine created without the flag. */
+int gossip_read_monger_counts(gossip_engine_t* eng, uint64_t* out, uint64_t n_words);
 /* ANTIENTROPY readout: the K versions of one node (owned by this shard), and its alive flag. */
 int gossip_read_versions(gossip_engine_t* eng, uint64_t node, uint32_t* out, uint32_t ncomp, uint32_t* alive);
 /* ANTIENTROPY readout of every owned row: out[i * K + c] for owned node lo + i. */
