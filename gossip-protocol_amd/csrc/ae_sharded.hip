@@ -15,7 +15,6 @@
 #include <type_traits>
 
 #include "philox.h"
-#include "topo_peers.h"
 #include "wave.h"
 
 namespace gossip {

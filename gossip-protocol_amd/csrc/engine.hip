@@ -311,10 +311,9 @@ int need_topo(gossip_engine* e) {
 
 // stall streaks after round t (random modes), over the peers that round drew
 int stall_after_round(gossip_engine* e, uint32_t t) {
-  if (e->topo_peers)
-    HIP_OK(e, launch_stall_update_topo(e->stall_d, e->N, e->k, t, e->key0, e->key1, e->fa, e->orow, e->ocol, e->stream));
-  else
-    HIP_OK(e, launch_stall_update(e->stall_d, e->N, e->k, t, e->key0, e->key1, e->fa, e->stream));
+  const uint32_t *orow = nullptr, *ocol = nullptr;  // uniform peers, whatever topology the engine holds
+  if (e->topo_peers) orow = e->orow, ocol = e->ocol;
+  HIP_OK(e, launch_stall_update(e->stall_d, e->N, e->k, t, e->key0, e->key1, e->fa, orow, ocol, e->stream));
   return GOSSIP_OK;
 }
 
@@ -1227,9 +1226,9 @@ int compute_round(gossip_engine* e, const uint64_t* gathered) {
     HIP_OK(e, hipMemcpyAsync(e->Snext, e->S, bytes, hipMemcpyDeviceToDevice, e->stream));
     if (e->monger) {  // rumor mongering: H moves with S
       HIP_OK(e, hipMemcpyAsync(e->hot_next, e->hot, bytes, hipMemcpyDeviceToDevice, e->stream));
-      const MongerArgs m{a, e->hot, e->hot_next, e->cool, e->blind, e->topo_peers};
-      if (e->counts) HIP_OK(e, launch_round_monger_count(MongerCountArgs{m, e->counts, e->limit}, e->stream));  // §2.14
-      else HIP_OK(e, launch_round_monger(m, e->stream));
+      // e->counts stays null until a limit above 1 is set: the counter forms (§2.14) run only from then on
+      const MongerArgs m{a, e->hot, e->hot_next, e->cool, e->blind, e->topo_peers, e->counts, e->limit};
+      HIP_OK(e, launch_round_monger(m, e->stream));
     } else if (e->topo_peers) {
       HIP_OK(e, launch_round_topo(a, e->stream));  // peers from the rows
     } else {

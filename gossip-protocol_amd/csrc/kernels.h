@@ -41,8 +41,9 @@ struct FloodWalks {
 hipError_t launch_round_random(const RoundArgs& a, hipStream_t st);
 hipError_t launch_round_flood_walks(const RoundArgs& a, const FloodWalks& fw, hipStream_t st);
 // Stall streaks after round t (random modes), all N nodes; fa.stall is the array.
+// The peers are resolved through the rows orow / ocol (§2.10), or uniform when orow is null.
 hipError_t launch_stall_update(uint8_t* stall, uint64_t N, uint32_t k, uint32_t t, uint32_t key0, uint32_t key1,
-                               const Faults& fa, hipStream_t st);
+                               const Faults& fa, const uint32_t* orow, const uint32_t* ocol, hipStream_t st);
 hipError_t launch_round_flood(const RoundArgs& a, hipStream_t st);
 hipError_t launch_stats(const RoundArgs& a, hipStream_t st);
 hipError_t launch_frontier(const uint64_t* S, const uint64_t* Sprev, uint64_t* F, uint64_t n, hipStream_t st);

@@ -9,6 +9,7 @@
 #include "kernels.h"
 #include "round.h"
 #include "philox.h"
+#include "wave.h"
 
 namespace gossip {
 
@@ -16,23 +17,12 @@ namespace {
 
 constexpr int kBlock = 256;
 
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // word w of global node n in the gathered [G][W][Nl] image
 template <bool ONE_WORD>
 __device__ __forceinline__ uint64_t gidx(uint64_t n, uint32_t w, uint64_t Nl, uint32_t W) {
   if (ONE_WORD) return n;
   const uint64_t r = n / Nl;
   return (r * W + w) * Nl + (n - r * Nl);
-}
-
-__device__ __forceinline__ uint64_t full_mask(uint32_t R, uint32_t w) {
-  const uint32_t bits = R - 64u * w;
-  return bits >= 64u ? ~0ull : ((1ull << bits) - 1ull);
 }
 
 // ---------------------------------------------------------------------------
@@ -145,7 +135,7 @@ __global__ __launch_bounds__(kBlock) void round_flood_kernel(RoundArgs a) {
       a.skip[li] = sk;
     }
   }
-  msgs = wave_sum_u64(msgs);
+  msgs = wave_sum64(msgs);
   if ((threadIdx.x & 63) == 0 && msgs) atomicAdd((unsigned long long*)&a.partial[2], (unsigned long long)msgs);
 }
 
@@ -201,7 +191,7 @@ __global__ __launch_bounds__(kBlock) void round_flood_walks_kernel(RoundArgs a, 
     fw.cur[i] = c;
     fw.att[i] = (uint8_t)at;
   }
-  msgs = wave_sum_u64(msgs);
+  msgs = wave_sum64(msgs);
   if ((threadIdx.x & 63) == 0 && msgs) atomicAdd((unsigned long long*)&a.partial[2], (unsigned long long)msgs);
 }
 
@@ -219,25 +209,38 @@ __global__ __launch_bounds__(kBlock) void flood_walks_learn_kernel(RoundArgs a, 
 }
 
 // Stall streaks after round t: a node not yet stalled counts the
-// round when any of its k exchanges was lost, else starts over.  Draws only: the
-// streaks never depend on S.
+// round when any of its k exchanges was lost, else starts over.  TOPO: the peers come
+// from the node's row (§2.10), and an empty row has no exchange to lose.  Draws (and
+// rows) only: the streaks never depend on S.
+template <bool TOPO>
 __global__ __launch_bounds__(kBlock) void stall_update_kernel(uint8_t* __restrict__ st, uint64_t N, uint32_t k,
-                                                              uint32_t t, uint32_t key0, uint32_t key1, Faults fa) {
+                                                              uint32_t t, uint32_t key0, uint32_t key1, Faults fa,
+                                                              const uint32_t* __restrict__ orow,
+                                                              const uint32_t* __restrict__ ocol) {
   fa.stall = nullptr;  // the partition block of a node that is not stalled
   const uint64_t nm1 = N - 1;
   for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += (uint64_t)gridDim.x * kBlock) {
     const uint32_t n = (uint32_t)i;
     const uint32_t c = st[i];
     if (c >= fa.D) continue;
-    const Reach rc = reach_of(n, fa);
+    uint32_t b = 0, d = 0;
+    if (TOPO) {
+      b = orow[n];
+      d = orow[n + 1] - b;
+    }
     bool any = false;
-    u32x4 x{0, 0, 0, 0}, lw{0, 0, 0, 0};
-    for (uint32_t j = 0; j < k && !any; ++j) {
-      if ((j & 3u) == 0) {
-        x = philox4x32_10(u32x4{n, t, 0u, j >> 2}, key0, key1);
-        if (fa.loss) lw = loss_draws(n, t, j >> 2, key0, key1);
+    if (!TOPO || d) {
+      const Reach rc = reach_of(n, fa);
+      u32x4 x{0, 0, 0, 0}, lw{0, 0, 0, 0};
+      for (uint32_t j = 0; j < k && !any; ++j) {
+        if ((j & 3u) == 0) {
+          x = philox4x32_10(u32x4{n, t, 0u, j >> 2}, key0, key1);
+          if (fa.loss) lw = loss_draws(n, t, j >> 2, key0, key1);
+        }
+        const uint32_t xj = lane_of(x, j & 3u);
+        const uint32_t p = TOPO ? ocol[b + topo_index_from_word(xj, d)] : peer_from_word(xj, nm1, n);
+        any = edge_lost(fa, rc, p, lane_of(lw, j & 3u));
       }
-      any = edge_lost(fa, rc, peer_from_word(lane_of(x, j & 3u), nm1, n), lane_of(lw, j & 3u));
     }
     st[i] = (uint8_t)(any ? c + 1 : 0);
   }
@@ -284,7 +287,7 @@ __global__ __launch_bounds__(kBlock) void stats_kernel(RoundArgs a) {
     }
     full += (uint32_t)__popcll(__ballot(isfull));
   }
-  hash = wave_sum_u64(hash);
+  hash = wave_sum64(hash);
   if (lane == 0) {
     red_hash[wave] = hash;
     red_full[wave] = full;
@@ -337,7 +340,7 @@ __global__ __launch_bounds__(kBlock) void hash_kernel(const uint64_t* S, uint64_
       const uint64_t x = S[(uint64_t)w * Nl + i];
       if (x) h += mix64(x + ((uint64_t)w * N + lo + i) * kGold64);
     }
-  h = wave_sum_u64(h);
+  h = wave_sum64(h);
   if ((threadIdx.x & 63) == 0 && h) atomicAdd((unsigned long long*)out, (unsigned long long)h);
 }
 
@@ -388,8 +391,10 @@ hipError_t launch_round_flood_walks(const RoundArgs& a, const FloodWalks& fw, hi
 }
 
 hipError_t launch_stall_update(uint8_t* stall, uint64_t N, uint32_t k, uint32_t t, uint32_t key0, uint32_t key1,
-                               const Faults& fa, hipStream_t st) {
-  stall_update_kernel<<<grid_for(N, 8192), kBlock, 0, st>>>(stall, N, k, t, key0, key1, fa);
+                               const Faults& fa, const uint32_t* orow, const uint32_t* ocol, hipStream_t st) {
+  const uint32_t grid = grid_for(N, 8192);
+  if (orow) stall_update_kernel<true><<<grid, kBlock, 0, st>>>(stall, N, k, t, key0, key1, fa, orow, ocol);
+  else stall_update_kernel<false><<<grid, kBlock, 0, st>>>(stall, N, k, t, key0, key1, fa, nullptr, nullptr);
   return hipGetLastError();
 }
 

@@ -27,14 +27,10 @@ struct MongerArgs {
   uint32_t cool;       // an edge's coin (stream tag 5) holds when its word is below this
   uint32_t blind;      // 0: feedback (a delivered push counts what the peer held), 1: every attempt counts
   bool topo;           // peers drawn from the rows (GOSSIP_FLAG_TOPO_PEERS) or from all N nodes
-};
-
-// The round with counters: bit r of plane b of C[n][r] at
-// C[(b * W + w) * N + n], r = 64 w + bit.  Only lane n reads or writes C[*][n].
-struct MongerCountArgs {
-  MongerArgs m;
-  uint64_t* C;     // [4][W][N], updated in place
-  uint32_t limit;  // 1..15: a rumor cools at a counted contact that leaves its count at or above this
+  // Counters, after the fields every engine has so that their offsets stay: bit r of
+  // plane b of C[n][r] at C[(b * W + w) * N + n], r = 64 w + bit.  Only lane n reads or writes C[*][n].
+  uint64_t* C;         // [4][W][N], updated in place; null: the engine holds no counters (the coin round)
+  uint32_t limit;      // 1..15: a rumor cools at a counted contact that leaves its count at or above this
 };
 
 // The cooling coins of edges 4q .. 4q + 3 of node n in round t: Philox stream tag 5.
@@ -43,11 +39,9 @@ __host__ __device__ __forceinline__ u32x4 cool_draws(uint32_t n, uint32_t t, uin
 }
 
 // One round: ORs the pushes into a.Snext and Hnext, clears the cooled bits of Hnext, and adds k per
-// initiating node to a.partial[2].
+// initiating node to a.partial[2].  With m.C set, a coin that holds adds one to the count of every
+// rumor of its counted set (saturating at 15), and a rumor cools when that leaves it at m.limit or more.
 hipError_t launch_round_monger(const MongerArgs& m, hipStream_t st);
-// The same round for an engine that holds counters: a coin that holds adds one to the count of every
-// rumor of its counted set (saturating at 15), and a rumor cools when that leaves it at c.limit or more.
-hipError_t launch_round_monger_count(const MongerCountArgs& c, hipStream_t st);
 // Client broadcast: node >= 0 sets one bit, node < 0 every rumor at its tag-2 origin; the bit is
 // set in H only where it is new in S (a cooled rumor is not re-heated).
 hipError_t launch_monger_inject(uint64_t* S, uint64_t* H, uint64_t N, uint32_t R, uint32_t key0, uint32_t key1,

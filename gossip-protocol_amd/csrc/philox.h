@@ -50,6 +50,12 @@ __host__ __device__ __forceinline__ uint32_t peer_from_word(uint32_t x, uint64_t
   return p + (p >= n ? 1u : 0u);
 }
 
+// Index into a row of d entries from one Philox word: floor(x * d / 2^32), one high-half
+// product (the scaling of peer_from_word, over the row instead of over [0, N) \ {n}).
+__host__ __device__ __forceinline__ uint32_t topo_index_from_word(uint32_t x, uint32_t d) {
+  return (uint32_t)(((uint64_t)x * d) >> 32);
+}
+
 // Fault model (the reference's lossy SyncRPC,
 // main.go:77-87): the edge n -> p_j(n) of round t is lost in both directions
 // when a partition separates its ends (nodes split into `parts` contiguous

@@ -7,6 +7,12 @@ namespace gossip {
 
 __device__ __forceinline__ uint64_t full_mask1(uint32_t R) { return R >= 64 ? ~0ull : ((1ull << R) - 1ull); }
 
+// the bits of word w that R rumors use (w < ceil(R / 64))
+__device__ __forceinline__ uint64_t full_mask(uint32_t R, uint32_t w) {
+  const uint32_t bits = R - 64u * w;
+  return bits >= 64u ? ~0ull : ((1ull << bits) - 1ull);
+}
+
 __device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

@@ -6,8 +6,9 @@ and beside each, at the same N and k, the uniform round of a GOSSIP_FLAG_DIRECT 
 kernel shape without the row load) and the FLOOD round over the same rows (the reference's own
 rule, main.go:65-89: every neighbour).  Each engine runs to convergence or `rounds` rounds, three
 times (the first untimed); the figure is device time per round from engine timer 0.  Writes one
-JSON file per topology into the output directory.
-Usage: topo_probe.py [--out DIR] [--log2 22] [--rounds 256]"""
+JSON file per topology into the output directory.  --pkg names another build's package directory to
+measure that one instead; --build is a name for it, echoed in the JSON.
+Usage: topo_probe.py [--out DIR] [--log2 22] [--rounds 256] [--pkg DIR [--build NAME]]"""
 import argparse
 import json
 import os
@@ -15,9 +16,9 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "gossip-protocol_amd"))
 import numpy as np  # noqa: E402
-from gossip_hip import FLAG_DIRECT, FLAG_TIMING, FLAG_TOPO_PEERS, Engine  # noqa: E402
+
+gh = None  # the measured build's gossip_hip, imported by main() from --pkg
 
 K, R, SEED = 2, 64, 0x5EED0007
 
@@ -43,7 +44,7 @@ def grid_topology(w):
 
 def measure(mode, flags, topo, n, rounds):
     """us per round (timer 0) of the last two of three runs, and what the last run did."""
-    e = Engine(n, R, mode, K, SEED, flags=flags | FLAG_TIMING)
+    e = gh.Engine(n, R, mode, K, SEED, flags=flags | gh.FLAG_TIMING)
     if topo is not None:
         e.set_topology(topo)
     for rep in range(3):
@@ -64,17 +65,22 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "topo_peers"))
     ap.add_argument("--log2", type=int, default=22)
     ap.add_argument("--rounds", type=int, default=256)
+    ap.add_argument("--build", default="this tree", help="a name for the measured build, echoed in the JSON")
+    ap.add_argument("--pkg", default=os.path.join(ROOT, "gossip-protocol_amd"))
     a = ap.parse_args()
+    global gh
+    sys.path.insert(0, a.pkg)
+    import gossip_hip as gh
     os.makedirs(a.out, exist_ok=True)
     n = 1 << a.log2
     for name, build in (("random8", lambda: random_topology(n, 8)), ("grid", lambda: grid_topology(1 << (a.log2 // 2)))):
         t0 = time.perf_counter()
         topo = build()
         assert topo[0].size - 1 == n
-        out = {"workload": f"{name}, N = 2^{a.log2}, pushpull k = {K}, R = {R} (W = 1)", "nodes": n,
+        out = {"build": a.build, "workload": f"{name}, N = 2^{a.log2}, pushpull k = {K}, R = {R} (W = 1)", "nodes": n,
                "edges": int(topo[1].size), "fanout": K, "rumors": R, "max_rounds": a.rounds,
-               "topo_peers": measure("pushpull", FLAG_TOPO_PEERS, topo, n, a.rounds),
-               "uniform_direct": measure("pushpull", FLAG_DIRECT, None, n, a.rounds),
+               "topo_peers": measure("pushpull", gh.FLAG_TOPO_PEERS, topo, n, a.rounds),
+               "uniform_direct": measure("pushpull", gh.FLAG_DIRECT, None, n, a.rounds),
                "flood": measure("flood", 0, topo, n, a.rounds)}
         out["topo_over_uniform_direct"] = out["topo_peers"]["us_per_round"] / out["uniform_direct"]["us_per_round"]
         out["topo_over_flood"] = out["topo_peers"]["us_per_round"] / out["flood"]["us_per_round"]
