@@ -18,20 +18,16 @@ constexpr uint32_t kTileD = 16384;   // destination tile (nodes): one 128 KiB LD
 constexpr uint32_t kTileDLog = 14;
 constexpr uint32_t kRecPerRegion = 16384;  // records staged per sender tile (LDS, 4 B each)
 constexpr uint32_t kMaxSenders = 8192;     // senders per sender tile (their values staged once, 8 B each)
-constexpr uint32_t kMaxTilesD = 4096;     // tiles with sender values staged in LDS (N <= 2^26); past it, up to
-                                          // kSbMaxTiles (2^27 nodes), emit re-reads them from S
+constexpr uint32_t kMaxTilesD = 4096;     // tile counters beside sender values staged in LDS (small regions)
 
-// Sharded dense rounds (sb_*): the pull pass stages no sender values, so its
-// tile counters cover the whole image (N <= kSbMaxTiles * kTileD = 2^27).
+// Tile counters of the emits that stage no sender values beside them: big regions (packed
+// 16-bit counters) and the sharded pull pass, whose tiles cover the whole image
+// (N <= kSbMaxTiles * kTileD = 2^27).
 constexpr uint32_t kSbMaxTiles = 8192;
 // one-shard rounds take the big regions (make_bin_geom(big)) past this many destination tiles
 // (2^24 nodes): the big emit costs more per sender, the walks gain more from longer runs
 constexpr uint32_t kBigFromTiles = 1024;
 
-// One emit pass of a sharded dense round: senders [snd0, snd0 + nsnd) (global
-// ids), edges whose peer lies in [dst0, dst0 + dstn), directions in dmask
-// (bit 0 push, bit 1 pull); wvals = 0: the records carry no sender value
-// (the pull pass).
 // Indices [lo, lo + n) with [skip0, skip1) spliced out: at(i) = lo + i, moved
 // past the hole.  A launch over part of the regions or tiles.
 struct IdxRange {
@@ -43,9 +39,12 @@ struct IdxRange {
   static IdxRange all(uint32_t n) { return IdxRange{0u, n, 0u, 0u}; }
 };
 
+// One emit pass of a sharded dense round: senders [snd0, snd0 + nsnd) (global
+// ids), edges whose peer lies in [dst0, dst0 + dstn), directions in dmask
+// (bit 0 push, bit 1 pull).
 struct EmitRange {
   uint64_t snd0, nsnd, dst0, dstn;
-  uint32_t dmask, wvals;
+  uint32_t dmask;
   IdxRange rs;  // sender regions of this launch
 };
 
@@ -62,8 +61,8 @@ struct BinGeom {
   uint32_t split;        // one shard: record ids as two u16 arrays (BinBufs::dst / src) instead of ids
 };
 
-// big: regions of up to 2 * kMaxSenders senders and 2 * kRecPerRegion records (one shard
-// past kMaxTilesD tiles: the emit's 16-bit packed tile counters, binned.hip V = 4)
+// big: regions of up to 2 * kMaxSenders senders and 2 * kRecPerRegion records (one shard past
+// kBigFromTiles tiles, sharded past kMaxTilesD image tiles: the emit's BIG forms, binned.hip)
 BinGeom make_bin_geom(uint64_t N, uint32_t k, bool big = false);
 bool bin_path_ok(uint64_t N, uint32_t k, uint32_t W, uint32_t G);
 

@@ -145,6 +145,26 @@ __device__ __forceinline__ uint32_t peer_filter(uint32_t d, uint32_t p, uint32_t
 // record flags: kIdVZ = no push on this record, kIdVF = no pull
 __device__ __forceinline__ uint32_t dir_flags(uint32_t d) { return ((d & 1u) ? 0u : kIdVZ) | ((d & 2u) ? 0u : kIdVF); }
 
+// The live edges n -> p of sender n in round t, fn(p, j) for each: one Philox draw per 4
+// edges; FAULTS: the loss draws and n's partition block too, and a lost edge is skipped (it
+// carries nothing in either direction).  The one walk of the emit's redrawn
+// passes and the exchange rounds' count and emit.
+template <bool FAULTS, typename F>
+__device__ __forceinline__ void live_edges(uint32_t k, uint32_t n, uint64_t nm1, uint32_t t, uint32_t key0,
+                                           uint32_t key1, const Faults& fa, F&& fn) {
+  u32x4 x{0, 0, 0, 0}, lw{0, 0, 0, 0};
+  const Reach rc = FAULTS ? reach_of(n, fa) : Reach{0u, 0xFFFFFFFFu};
+  for (uint32_t j = 0; j < k; ++j) {
+    if ((j & 3u) == 0) {
+      x = philox4x32_10(u32x4{n, t, 0u, j >> 2}, key0, key1);
+      if (FAULTS && fa.loss) lw = loss_draws(n, t, j >> 2, key0, key1);
+    }
+    const uint32_t p = peer_from_word(lane_of(x, j & 3u), nm1, n);
+    if (FAULTS && edge_lost(fa, rc, p, lane_of(lw, j & 3u))) continue;
+    fn(p, j);
+  }
+}
+
 // Region counting sort, middle step: cur[0, nt) holds the records per
 // destination tile; writes each run's start to off_row[0, nt] (u16, the total
 // last), turns cur into the fill pointers and returns the total.  Every thread
@@ -232,35 +252,36 @@ __device__ __forceinline__ uint32_t region_offsets_packed(uint32_t* cur, uint32_
   return total;
 }
 
-// KREG > 0: the k (<= KREG) peers of each sender stay in registers between passes.
+// Where pass B (placement) gets the peers that pass A (count) drew.  Kept peers need k <=
+// kKeptPeers (one Philox draw per sender instead of two).
+enum class Peers {
+  Redrawn,  // the same draws and probes again
+  InRegs,   // kept in registers (small regions: 8 senders per lane)
+  InLds,    // kept in the LDS staging room, {p0, p1, dirs} in a u64 (p < 2^27), free until placement
+};
+constexpr int kKeptPeers = 2;
+
+// SHARD: one pass of a sharded dense round (EmitRange): senders [snd0, snd0 + nsnd) of the
+//   gathered image S (global ids), only edges whose peer lies in [dst0, dst0 + dstn), only the
+//   directions in dmask, tiles counted from dst0, u32 ids; else one shard, split u16 ids.
+// BIG: regions twice as large (up to 16384 senders, 32768 records; 16-bit tile counters packed
+//   in pairs make the room), so the runs stay twice as long; on-chip write-out; no next-region
+//   prefetch (its registers).  One shard: regions from the queue, pushes packed (BinGeom::aos).
+// VALS: the records carry the sender values (all but the sharded pull pass, whose tile counters
+//   can therefore cover kSbMaxTiles tiles of the whole image at either region size).
 // FAULTS: edge loss / partitions active; off, none of that code exists.
-// V = 0: one shard.  V = 1, 2: one pass of a sharded dense round (EmitRange):
-// senders [snd0, snd0 + nsnd) of the gathered image S (global ids), only edges
-// whose peer lies in [dst0, dst0 + dstn), only the directions in dmask, tiles
-// counted from dst0.  V = 2 (pull pass) stores no sender values, so its tile
-// counters can cover kSbMaxTiles tiles of the whole image.  V = 3: one shard
-// past 4096 tiles (N > 2^26): the sender values are not staged in LDS (the
-// tile counters take that room) but re-read from S — the region's slice, which
-// this block has just streamed, so the reads hit L2.  V = 4: as V = 3 with regions
-// twice as large (up to 16384 senders, 32768 records; 16-bit tile counters packed in
-// pairs make the room), so the runs stay twice as long at N > 2^26; no next-region
-// prefetch (its registers).  V = 6, 7: the big regions of V = 4 for the sharded passes of
-// V = 1 (push, values written beside the u32 ids) and V = 2 (pull, no values); V = 8, 9: the
-// same with V = 5's peers kept between the passes (no faults, k <= 2).
-template <int KREG, bool FAULTS, int V>
+template <bool SHARD, bool BIG, bool VALS, Peers PEERS, bool FAULTS>
 __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const uint64_t* __restrict__ S, BinBufs b,
                                                                   uint32_t R, uint32_t t, uint32_t key0,
                                                                   uint32_t key1, uint32_t mode, uint32_t filt,
                                                                   Faults fa, EmitRange er) {
-  constexpr bool SHARD = V == 1 || V == 2 || V >= 6;
-  constexpr bool STAGE = V == 0 || V == 1;  // sender values staged in LDS
-  constexpr bool BIG = V >= 4;               // packed 16-bit tile counters, double regions
-  // V = 5: BIG without faults, k <= 2 (the launch checks): the count pass keeps each sender's
-  // peers and edge directions in the LDS staging room ({p0, p1, dirs} in a u64: p < 2^27), so
-  // the placement pass draws no Philox again (one cipher per sender instead of two)
-  constexpr bool PKC = V == 5 || V == 8 || V == 9;
-  constexpr bool NOVALS = V == 7 || V == 9;  // the sharded pull pass writes no sender values
-  constexpr uint32_t kMaxT = V >= 2 ? kSbMaxTiles : kMaxTilesD;
+  static_assert(SHARD || VALS, "only a sharded pull pass leaves the values out");
+  // 16 senders per lane keep no room for their peers in registers (78 VGPRs spilled)
+  static_assert(PEERS != Peers::InRegs || !BIG, "peers kept in registers: small regions only");
+  static_assert(PEERS != Peers::InLds || (BIG && !FAULTS), "peers kept in LDS: big regions without faults");
+  constexpr int KREG = PEERS == Peers::InRegs ? kKeptPeers : 0;
+  constexpr bool STAGE = !BIG && VALS;  // sender values staged in LDS
+  constexpr uint32_t kMaxT = BIG || !VALS ? kSbMaxTiles : kMaxTilesD;
   constexpr uint32_t kMaxS = BIG ? 2 * kMaxSenders : kMaxSenders;
   __shared__ uint32_t cur[BIG ? kMaxT / 2 : kMaxT];
   __shared__ __align__(16) uint32_t st_ids[BIG ? 2 * kRecPerRegion : kRecPerRegion];  // p_local | n_local << 14, by tile (BIG: then the u64 sender values)
@@ -295,7 +316,7 @@ __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const
     }
   };
   uint64_t v[kQ], vn[kQ];
-  // regions r = blockIdx.x, +gridDim.x, ... of the launch; V != 0 launches may
+  // regions r = blockIdx.x, +gridDim.x, ... of the launch; sharded launches may
   // cover a subrange of the regions (er.rs: the part of a dense sharded round
   // that overlaps the all-gather, or the rest)
   const uint32_t nr = SHARD ? er.rs.n : g.nt_s;
@@ -345,7 +366,7 @@ __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const
   // pass A: per-destination-tile counts of the records (edges that carry something)
   uint32_t pr[KREG > 0 ? kQ * KREG : 1];
   uint32_t ed[KREG > 0 ? kQ : 1];  // 2 bits per edge j: directions (sender_dirs, then peer_filter)
-  if (KREG > 0) {
+  if (PEERS == Peers::InRegs) {
 #pragma unroll
     for (uint32_t q = 0; q < kQ; ++q) {
       const uint32_t i = tid + q * kEmitThreads;
@@ -406,7 +427,7 @@ __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const
           tile_of(pr[q * KREG + j], &tl, &pl);
           count_tile(tl);
         }
-  } else if (PKC) {
+  } else if (PEERS == Peers::InLds) {
     uint64_t* pkl = (uint64_t*)st_ids;  // kMaxS u64 = the staging room, free until placement
 #pragma unroll
     for (uint32_t q = 0; q < kQ; ++q) {
@@ -417,7 +438,7 @@ __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const
         const uint32_t n = (uint32_t)(snd0 + base + i);
         const u32x4 x = philox4x32_10(u32x4{n, t, 0u, 0u}, key0, key1);
 #pragma unroll
-        for (uint32_t j = 0; j < 2; ++j) {
+        for (uint32_t j = 0; j < kKeptPeers; ++j) {
           if (j >= g.k) break;
           const uint32_t p = peer_from_word(lane_of(x, j), nm1, n);
           uint32_t tl, pl;
@@ -436,20 +457,10 @@ __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const
       if (i >= nsend) break;
       const uint32_t d = sender_dirs(mode, v[q], fm) & dmask;
       if (!d) continue;
-      const uint32_t n = (uint32_t)(snd0 + base + i);
-      u32x4 x{0, 0, 0, 0}, lw{0, 0, 0, 0};
-      const Reach rc = FAULTS ? reach_of(n, fa) : Reach{0u, 0xFFFFFFFFu};  // n's partition block (§2.8)
-      for (uint32_t j = 0; j < g.k; ++j) {
-        if ((j & 3u) == 0) {
-          x = philox4x32_10(u32x4{n, t, 0u, j >> 2}, key0, key1);
-          if (FAULTS && fa.loss) lw = loss_draws(n, t, j >> 2, key0, key1);
-        }
-        const uint32_t p = peer_from_word(lane_of(x, j & 3u), nm1, n);
-        if (FAULTS && edge_lost(fa, rc, p, lane_of(lw, j & 3u))) continue;
+      live_edges<FAULTS>(g.k, (uint32_t)(snd0 + base + i), nm1, t, key0, key1, fa, [&](uint32_t p, uint32_t) {
         uint32_t tl, pl;
-        if (!tile_of(p, &tl, &pl)) continue;
-        if (peer_filter(d, p, filt, b.nzb, b.fullb)) count_tile(tl);
-      }
+        if (tile_of(p, &tl, &pl) && peer_filter(d, p, filt, b.nzb, b.fullb)) count_tile(tl);
+      });
     }
   }
   __syncthreads();
@@ -458,23 +469,25 @@ __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const
   const uint32_t total = BIG ? region_offsets_packed(cur, g.nt_d, off_row, wsum, wpre)
                              : region_offsets(cur, g.nt_d, off_row, wsum, wpre);
 
-  // pass B: each record to its slot (k <= KREG: the peers and directions from
-  // registers; else the same draws and probes again)
-  if (KREG > 0) {
+  // pass B: each record to its slot (the peers and directions as pass A kept them, or
+  // the same draws and probes again)
+  auto place = [&](uint32_t p, uint32_t i, uint32_t d) {  // sender i's edge to p (inside the range), directions d
+    uint32_t tl, pl;
+    tile_of(p, &tl, &pl);
+    const uint32_t pos = place_tile(tl);
+    st_ids[pos] = pl | (i << kTileDLog) | dir_flags(d);
+  };
+  if (PEERS == Peers::InRegs) {
 #pragma unroll
     for (uint32_t q = 0; q < kQ; ++q) {
       const uint32_t i = tid + q * kEmitThreads;
 #pragma unroll
       for (int j = 0; j < KREG; ++j) {
         const uint32_t d = (ed[q] >> (2 * j)) & 3u;
-        if (!d) continue;
-        uint32_t tl, pl;
-        tile_of(pr[q * KREG + j], &tl, &pl);
-        const uint32_t pos = place_tile(tl);
-        st_ids[pos] = pl | (i << kTileDLog) | dir_flags(d);
+        if (d) place(pr[q * KREG + j], i, d);
       }
     }
-  } else if (PKC) {
+  } else if (PEERS == Peers::InLds) {
     uint64_t mine[kQ];
 #pragma unroll
     for (uint32_t q = 0; q < kQ; ++q) mine[q] = ((const uint64_t*)st_ids)[tid + q * kEmitThreads];
@@ -483,14 +496,9 @@ __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const
     for (uint32_t q = 0; q < kQ; ++q) {
       const uint32_t i = tid + q * kEmitThreads;
 #pragma unroll
-      for (uint32_t j = 0; j < 2; ++j) {
+      for (uint32_t j = 0; j < kKeptPeers; ++j) {
         const uint32_t dd = (uint32_t)(mine[q] >> (54 + 2 * j)) & 3u;
-        if (!dd) continue;
-        const uint32_t p = (uint32_t)(mine[q] >> (27 * j)) & ((1u << 27) - 1u);
-        uint32_t tl, pl;
-        tile_of(p, &tl, &pl);
-        const uint32_t pos = place_tile(tl);
-        st_ids[pos] = pl | (i << kTileDLog) | dir_flags(dd);
+        if (dd) place((uint32_t)(mine[q] >> (27 * j)) & ((1u << 27) - 1u), i, dd);
       }
     }
   } else {
@@ -499,23 +507,12 @@ __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const
       if (i >= nsend) break;
       const uint32_t d0 = sender_dirs(mode, v[q], fm) & dmask;
       if (!d0) continue;
-      const uint32_t n = (uint32_t)(snd0 + base + i);
-      u32x4 x{0, 0, 0, 0}, lw{0, 0, 0, 0};
-      const Reach rc = FAULTS ? reach_of(n, fa) : Reach{0u, 0xFFFFFFFFu};  // n's partition block (§2.8)
-      for (uint32_t j = 0; j < g.k; ++j) {
-        if ((j & 3u) == 0) {
-          x = philox4x32_10(u32x4{n, t, 0u, j >> 2}, key0, key1);
-          if (FAULTS && fa.loss) lw = loss_draws(n, t, j >> 2, key0, key1);
-        }
-        const uint32_t p = peer_from_word(lane_of(x, j & 3u), nm1, n);
-        if (FAULTS && edge_lost(fa, rc, p, lane_of(lw, j & 3u))) continue;
+      live_edges<FAULTS>(g.k, (uint32_t)(snd0 + base + i), nm1, t, key0, key1, fa, [&](uint32_t p, uint32_t) {
         uint32_t tl, pl;
-        if (!tile_of(p, &tl, &pl)) continue;
+        if (!tile_of(p, &tl, &pl)) return;
         const uint32_t d = peer_filter(d0, p, filt, b.nzb, b.fullb);
-        if (!d) continue;
-        const uint32_t pos = place_tile(tl);
-        st_ids[pos] = pl | (i << kTileDLog) | dir_flags(d);
-      }
+        if (d) place(p, i, d);
+      });
     }
   }
   __syncthreads();
@@ -524,8 +521,6 @@ __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const
   uint64_t* gvals = b.vals + (size_t)s * g.rp;
   uint16_t* gdst = b.dst + (size_t)s * g.rp;
   uint16_t* gsrc = b.src + (size_t)s * g.rp;
-  // the one-shard emits (BinGeom::split); V = 1, 2, 6, 7: sharded passes (u32 ids)
-  constexpr bool split = !SHARD;
   if constexpr (BIG) {
     // ids out first, then the region's sender values take the staging room and each
     // push is written packed {value, id} (BinGeom::aos), its value read from LDS: the
@@ -536,7 +531,7 @@ __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const
     // of a record is written in one loop and nothing is read back from the region: the
     // read-back missed L2 (18.5 M -> 8.4 M memory read requests per 2^27 launch, emit 1492 ->
     // 1136 us: profiles/emit_onchip/).
-    if constexpr (NOVALS) {  // V = 7, 9: ids only, straight from the staging room
+    if constexpr (!VALS) {  // ids only, straight from the staging room
       for (uint32_t e = tid; e < total; e += kEmitThreads) rec_st(&gids[e], st_ids[e]);
     } else {
       constexpr uint32_t kIdsPerLane = 2 * kRecPerRegion / kEmitThreads;
@@ -554,7 +549,7 @@ __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const
       __syncthreads();  // every staged id is in registers
       __asm__ volatile("" : "=v"(lid) : "0"(tid));
       uint64_t* sv = (uint64_t*)st_ids;  // 2 * kRecPerRegion u32 = kMaxS u64
-      // (V = 5 keeps v[] live through the count pass rather than rereading S here: 5.86 vs
+      // (the one-shard form with peers in LDS keeps v[] live through the count pass rather than rereading S here: 5.86 vs
       // 5.98 ms per 2^27 dense round, profiles/r04_e/summary.txt)
 #pragma unroll
       for (uint32_t q = 0; q < kQ; ++q) sv[tid + q * kEmitThreads] = v[q];
@@ -570,7 +565,7 @@ __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const
         for (uint32_t c = 0; c < kGroup; ++c) {
           const uint32_t e = lid + (j0 + c) * kEmitThreads, id = idr[j0 + c];
           if (e >= total) continue;
-          if constexpr (SHARD) {  // V = 6, 8: every value slot beside its u32 id (no holes)
+          if constexpr (SHARD) {  // every value slot beside its u32 id (no holes)
             rec_st(&gids[e], id);
             rec_st(&gvals[e], x[c]);
           } else {  // (one-shard big regions always pack: g.aos)
@@ -589,16 +584,13 @@ __global__ __launch_bounds__(kEmitThreads) void bin_emit_kernel(BinGeom g, const
     // every value slot is stored (also where the flags say no push), so the
     // region is written without holes (a partly written 64-B chunk costs HBM
     // a read-modify-write: profiles/r01_experiments/microbench5_scattered_pieces.jsonl)
-    if (split) {
+    if (!SHARD) {  // (BinGeom::split)
       rec_st(&gdst[e], dst_of(id));
       rec_st(&gsrc[e], src_of(id));
     } else {
       rec_st(&gids[e], id);
     }
-    if (STAGE) {
-      rec_st(&gvals[e], sval[(id >> kTileDLog) & kIdNMask]);
-    }
-    if (V >= 3) rec_st(&gvals[e], S[base + ((id >> kTileDLog) & kIdNMask)]);
+    if (STAGE) rec_st(&gvals[e], sval[(id >> kTileDLog) & kIdNMask]);
   }
   if constexpr (!BIG) {
 #pragma unroll
@@ -913,14 +905,18 @@ constexpr int kServeU = 8, kServeRPL = 2, kPushRPL = 1;
 
 // The pushes aimed at tile X (its runs in every sender region) ORed into acc,
 // by the waves [0, nwaves) (0: all).  VZ: the record id's no-push flag.
-// LAYOUT 0: u32 ids + values (sharded passes), 1: split u16 ids + values, 2: split + packed pushes
-template <uint32_t VZ, int LAYOUT>
+enum class RecLayout {
+  Ids32,        // u32 ids + values (sharded passes, exchange rounds)
+  Split,        // split u16 ids + values
+  SplitPacked,  // split u16 ids + packed pushes (BinGeom::aos)
+};
+template <uint32_t VZ, RecLayout LAYOUT>
 __device__ __forceinline__ void push_walk(const BinGeom& g, const BinBufs& b, uint32_t X, unsigned long long* acc,
                                           uint64_t* wmask, int32_t* wlist, uint32_t nwaves) {
   const uint32_t* __restrict__ gids = b.ids;
   const uint64_t* __restrict__ gvals = b.vals;
   const uint32_t* __restrict__ gprec = b.prec;
-  constexpr bool aos = LAYOUT == 2, SPLIT = LAYOUT >= 1;
+  constexpr bool aos = LAYOUT == RecLayout::SplitPacked, SPLIT = LAYOUT != RecLayout::Ids32;
   const uint16_t* rowb = b.offT + (size_t)X * g.nt_s;
   constexpr int U = kUnrollPipe;
   for_each_run_record_pipe<U, PushBuf<U>, kPushRPL>(g, rowb, rowb + g.nt_s, wmask, wlist, [&](const int32_t* rec) {
@@ -1054,7 +1050,7 @@ uint32_t serve_grid(uint32_t tiles, uint32_t cap = kServeGrid) { return cap == 0
 // bq.  Sharded dense round: g/b the push pass (every sender, tiles of the own
 // nodes), gq/bq the pull pass (own senders, tiles of the whole image); S and
 // Snext are the own slices (Nn nodes, global ids from hid0).
-template <int LAYOUT>
+template <RecLayout LAYOUT>
 __global__ __launch_bounds__(kTileThreads) void bin_apply_kernel(BinGeom g, BinBufs b, BinGeom gq, BinBufs bq,
                                                                   const uint64_t* S, uint64_t* Snext,  // may alias
                                                                   uint64_t Nn, uint64_t hid0,
@@ -1107,7 +1103,7 @@ __global__ __launch_bounds__(kTileThreads) void bin_apply_kernel(BinGeom g, BinB
   const bool do_pull = (mode == 2 || mode == 3) && (!split || wave >= pw);
   // split: waves [0, pw) walk the pushes, the others the responses
   const uint32_t qt0 = split ? pw * 64 : 0u, qnt = split ? kTileThreads - pw * 64 : kTileThreads;
-  constexpr bool SPLIT = LAYOUT >= 1;
+  constexpr bool SPLIT = LAYOUT != RecLayout::Ids32;
   if (do_push) push_walk<kIdVZ, LAYOUT>(g, b, X, acc, wmask, wlist, split ? pw : 0u);  // pushes aimed at this tile
   if (do_pull) {  // responses owed to this tile's own senders
     const uint32_t* __restrict__ qids = bq.ids;
@@ -1190,7 +1186,7 @@ BinGeom make_bin_geom(uint64_t N, uint32_t k, bool big) {
 bool bin_path_ok(uint64_t N, uint32_t k, uint32_t W, uint32_t G) {
   if (W != 1 || G != 1 || k == 0 || k > 64 || N < 2) return false;
   const BinGeom g = make_bin_geom(N, k);
-  // past 4096 tiles the emit re-reads sender values from S (V = 3); record indices are int32
+  // the emit's tile counters; record indices are int32
   return g.nt_d <= kSbMaxTiles && (uint64_t)g.nt_s * g.rp < (1ull << 31);
 }
 
@@ -1232,32 +1228,51 @@ void bin_carve(const BinGeom& g, void* base, BinBufs* b) {
 }
 
 namespace {
+// One emit launch over `regions` sender regions (one shard: er = EmitRange{}).
+struct EmitArgs {
+  const BinGeom& g;
+  const BinBufs& b;
+  const uint64_t* S;
+  uint32_t R, t, key0, key1, mode, filt;
+  const Faults& fa;
+  const EmitRange& er;
+  uint32_t regions;
+  hipStream_t st;
+};
+template <bool SHARD, bool BIG, bool VALS, Peers PEERS, bool FAULTS>
+void emit_as(const EmitArgs& a) {
+  const uint32_t eg = a.regions < kEmitGrid ? a.regions : kEmitGrid;  // persistent: one block per CU
+  bin_emit_kernel<SHARD, BIG, VALS, PEERS, FAULTS>
+      <<<eg, kEmitThreads, 0, a.st>>>(a.g, a.S, a.b, a.R, a.t, a.key0, a.key1, a.mode, a.filt, a.fa, a.er);
+}
+// The form of an emit launch, chosen here and nowhere else.  Regions: big when the geometry
+// was made so (make_bin_geom(big)).  Peers: kept between the passes when k <= kKeptPeers, in
+// registers with small regions, in LDS with big regions and no faults (the fault path has no
+// such form); else drawn again.  21 forms: (one shard | push pass | pull pass) x these 7.
+template <bool SHARD, bool VALS>
+void emit_pick(const EmitArgs& a) {
+  const bool big = a.g.ts > kMaxSenders || a.g.rp > kRecPerRegion;
+  const bool kept = a.g.k <= (uint32_t)kKeptPeers, faults = a.fa.any();
+  if (big && faults) emit_as<SHARD, true, VALS, Peers::Redrawn, true>(a);
+  else if (big && kept) emit_as<SHARD, true, VALS, Peers::InLds, false>(a);
+  else if (big) emit_as<SHARD, true, VALS, Peers::Redrawn, false>(a);
+  else if (kept && faults) emit_as<SHARD, false, VALS, Peers::InRegs, true>(a);
+  else if (kept) emit_as<SHARD, false, VALS, Peers::InRegs, false>(a);
+  else if (faults) emit_as<SHARD, false, VALS, Peers::Redrawn, true>(a);
+  else emit_as<SHARD, false, VALS, Peers::Redrawn, false>(a);
+}
+// shard: a pass of a sharded round (a.er); vals: its records carry the sender values
+void launch_emit(const EmitArgs& a, bool shard, bool vals) {
+  if (!shard) emit_pick<false, true>(a);
+  else if (vals) emit_pick<true, true>(a);
+  else emit_pick<true, false>(a);
+}
+
 // K1 + the run-offset transpose of a one-shard dense round
 void launch_bin_emit(const BinGeom& g, const BinBufs& b, uint64_t* S, uint64_t* partial, uint32_t R, uint32_t t,
                      uint32_t key0, uint32_t key1, uint32_t mode, uint32_t filt, const Faults& fa,
                      const RoundSync& rs, hipStream_t st) {
-  const uint32_t eg = g.nt_s < kEmitGrid ? g.nt_s : kEmitGrid;  // persistent: one block per CU
-#define GOSSIP_EMIT(KR, F, VV) \
-  bin_emit_kernel<KR, F, VV><<<eg, kEmitThreads, 0, st>>>(g, S, b, R, t, key0, key1, mode, filt, fa, EmitRange{})
-#define GOSSIP_EMIT_V(VV)                                                 \
-  if (g.k <= 2) {                                                        \
-    if (fa.any()) GOSSIP_EMIT(2, true, VV); else GOSSIP_EMIT(2, false, VV); \
-  } else {                                                                \
-    if (fa.any()) GOSSIP_EMIT(0, true, VV); else GOSSIP_EMIT(0, false, VV); \
-  }
-  if (g.ts > kMaxSenders || g.rp > kRecPerRegion) {  // make_bin_geom(big): V = 4, 5
-    // 16 senders per lane keep no room for their peers in registers (KREG = 2 spills 78
-    // VGPRs): V = 5 keeps them in LDS between the passes, V = 4 draws them again
-    if (fa.any()) GOSSIP_EMIT(0, true, 4);
-    else if (g.k <= 2) GOSSIP_EMIT(0, false, 5);
-    else GOSSIP_EMIT(0, false, 4);
-  } else if (g.nt_d <= kMaxTilesD) {
-    GOSSIP_EMIT_V(0)
-  } else {
-    GOSSIP_EMIT_V(3)
-  }
-#undef GOSSIP_EMIT_V
-#undef GOSSIP_EMIT
+  launch_emit(EmitArgs{g, b, S, R, t, key0, key1, mode, filt, fa, EmitRange{}, g.nt_s, st}, false, true);
   launch_transpose_u16(b.off, b.offT, g.nt_s, g.nt_d + 1, partial, rs.plen, st, b.dyn);
 }
 }  // namespace
@@ -1279,11 +1294,14 @@ hipError_t launch_binned_round(const BinGeom& g, const BinBufs& b, uint64_t* S, 
   // responses come from the record buffers), and K1/K2 have finished reading S_t
   if (!(parts & 4u)) return hipGetLastError();
   if (g.aos)
-    bin_apply_kernel<2><<<apply_grid(g), kTileThreads, 0, st>>>(g, b, g, b, S, S, g.N, 0, partial, R, mode, flags);
+    bin_apply_kernel<RecLayout::SplitPacked>
+        <<<apply_grid(g), kTileThreads, 0, st>>>(g, b, g, b, S, S, g.N, 0, partial, R, mode, flags);
   else if (g.split)
-    bin_apply_kernel<1><<<apply_grid(g), kTileThreads, 0, st>>>(g, b, g, b, S, S, g.N, 0, partial, R, mode, flags);
+    bin_apply_kernel<RecLayout::Split>
+        <<<apply_grid(g), kTileThreads, 0, st>>>(g, b, g, b, S, S, g.N, 0, partial, R, mode, flags);
   else
-    bin_apply_kernel<0><<<apply_grid(g), kTileThreads, 0, st>>>(g, b, g, b, S, S, g.N, 0, partial, R, mode, flags);
+    bin_apply_kernel<RecLayout::Ids32>
+        <<<apply_grid(g), kTileThreads, 0, st>>>(g, b, g, b, S, S, g.N, 0, partial, R, mode, flags);
   return hipGetLastError();  // the engine enqueues the round's snapshot (round.h) after its timing event
 }
 
@@ -1339,39 +1357,16 @@ IdxRange rest_of(uint32_t n, const IdxRange& x) { return IdxRange{0u, n - x.n, x
 void sb_emit(const BinGeom& gg, const BinBufs& bb, const uint64_t* image, uint32_t R, uint32_t t, uint32_t key0,
              uint32_t key1, uint32_t mode, const Faults& fa, const EmitRange& er, bool vals, hipStream_t st) {
   if (er.rs.n == 0) return;
-  const uint32_t eg = er.rs.n < kEmitGrid ? er.rs.n : kEmitGrid;
-#define GOSSIP_EMIT(KR, F, VV) \
-  bin_emit_kernel<KR, F, VV><<<eg, kEmitThreads, 0, st>>>(gg, image, bb, R, t, key0, key1, mode, 0u, fa, er)
-#define GOSSIP_EMIT_V(VV)                                                 \
-  if (gg.k <= 2) {                                                        \
-    if (fa.any()) GOSSIP_EMIT(2, true, VV); else GOSSIP_EMIT(2, false, VV); \
-  } else {                                                                \
-    if (fa.any()) GOSSIP_EMIT(0, true, VV); else GOSSIP_EMIT(0, false, VV); \
-  }
-  if (gg.ts > kMaxSenders || gg.rp > kRecPerRegion) {  // big regions (make_sb_geom): V = 6-9
-    if (fa.any()) {
-      if (vals) GOSSIP_EMIT(0, true, 6); else GOSSIP_EMIT(0, true, 7);
-    } else if (gg.k <= 2) {
-      if (vals) GOSSIP_EMIT(0, false, 8); else GOSSIP_EMIT(0, false, 9);
-    } else {
-      if (vals) GOSSIP_EMIT(0, false, 6); else GOSSIP_EMIT(0, false, 7);
-    }
-  } else if (vals) {
-    GOSSIP_EMIT_V(1)
-  } else {
-    GOSSIP_EMIT_V(2)
-  }
-#undef GOSSIP_EMIT_V
-#undef GOSSIP_EMIT
+  launch_emit(EmitArgs{gg, bb, image, R, t, key0, key1, mode, 0u, fa, er, er.rs.n, st}, true, vals);
 }
 
 void sb_transpose(const BinGeom& gg, const BinBufs& bb, uint64_t* partial, hipStream_t st) {
   launch_transpose_u16(bb.off, bb.offT, gg.nt_s, gg.nt_d + 1, partial, 0u, st);
 }
 
-EmitRange push_range(const SbGeom& g, const IdxRange& rs) { return EmitRange{0, g.p.N, g.lo, g.nown, 1u, 1u, rs}; }
+EmitRange push_range(const SbGeom& g, const IdxRange& rs) { return EmitRange{0, g.p.N, g.lo, g.nown, 1u, rs}; }
 EmitRange pull_range(const SbGeom& g) {
-  return EmitRange{g.lo, g.nown, 0, g.q.N, 2u, 0u, IdxRange::all(g.q.nt_s)};
+  return EmitRange{g.lo, g.nown, 0, g.q.N, 2u, IdxRange::all(g.q.nt_s)};
 }
 }  // namespace
 
@@ -1404,8 +1399,8 @@ hipError_t launch_sb_post(const SbGeom& g, const SbBufs& b, const uint64_t* imag
   BinBufs bp = b.p;
   bp.nzb = nzb;
   bp.fullb = fullb;
-  bin_apply_kernel<0><<<apply_grid(g.p), kTileThreads, 0, st>>>(g.p, bp, g.q, b.q, image + g.lo, Snext, g.nown, g.lo, partial,
-                                                      R, mode, flags);
+  bin_apply_kernel<RecLayout::Ids32><<<apply_grid(g.p), kTileThreads, 0, st>>>(
+      g.p, bp, g.q, b.q, image + g.lo, Snext, g.nown, g.lo, partial, R, mode, flags);
   return hipGetLastError();
 }
 
@@ -1452,24 +1447,6 @@ __device__ __forceinline__ uint32_t xd_filter(const XdFilter& xf, uint32_t d, ui
   return d;
 }
 
-// the live edges n -> p of sender n in round t (draws as bin_emit's; a lost edge
-// carries nothing in either direction)
-template <bool FAULTS, typename F>
-__device__ __forceinline__ void xd_edges(uint32_t k, uint32_t n, uint64_t nm1, uint32_t t, uint32_t key0,
-                                         uint32_t key1, const Faults& fa, F&& fn) {
-  u32x4 x{0, 0, 0, 0}, lw{0, 0, 0, 0};
-  const Reach rc = FAULTS ? reach_of(n, fa) : Reach{0u, 0xFFFFFFFFu};
-  for (uint32_t j = 0; j < k; ++j) {
-    if ((j & 3u) == 0) {
-      x = philox4x32_10(u32x4{n, t, 0u, j >> 2}, key0, key1);
-      if (FAULTS && fa.loss) lw = loss_draws(n, t, j >> 2, key0, key1);
-    }
-    const uint32_t p = peer_from_word(lane_of(x, j & 3u), nm1, n);
-    if (FAULTS && edge_lost(fa, rc, p, lane_of(lw, j & 3u))) continue;
-    fn(p, j);
-  }
-}
-
 // items per (sender region, owner of the peer).  (Reading the senders' classes from the
 // occupancy bitmaps instead of S_t made count + emit slower: S_t streamed here is still
 // in the MALL when emit reads it, profiles/r02_xd/variants3.)
@@ -1493,7 +1470,7 @@ __global__ __launch_bounds__(kEmitThreads) void xd_count_kernel(XdGeom g, const 
       const uint32_t d = sender_dirs(mode, S[base + i], fm);
       uint32_t keep = 0;  // filtered rounds: edge j survives the class probe (emit reads it, no second probe)
       if (d)
-        xd_edges<FAULTS>(g.k, (uint32_t)(g.lo + base + i), nm1, t, key0, key1, fa, [&](uint32_t p, uint32_t j) {
+        live_edges<FAULTS>(g.k, (uint32_t)(g.lo + base + i), nm1, t, key0, key1, fa, [&](uint32_t p, uint32_t j) {
           const uint32_t o = xd_owner(p, Nl32, g.G);
           if (xf.filt && !xd_filter(xf, d, o, p - o * Nl32)) return;
           keep |= 1u << j;
@@ -1563,7 +1540,7 @@ __global__ __launch_bounds__(kEmitThreads) void xd_emit_kernel(XdGeom g, const u
       const uint32_t d = sender_dirs(mode, S[base + i], fm);
       if (!d) continue;
       const uint32_t keep = xf.filt ? xf.keep[base + i] : ~0u;
-      xd_edges<FAULTS>(g.k, (uint32_t)(g.lo + base + i), nm1, t, key0, key1, fa, [&](uint32_t p, uint32_t j) {
+      live_edges<FAULTS>(g.k, (uint32_t)(g.lo + base + i), nm1, t, key0, key1, fa, [&](uint32_t p, uint32_t j) {
         if (!((keep >> j) & 1u)) return;  // dropped by the count pass's class probe
         const uint32_t o = xd_owner(p, Nl32, G), pl = p - o * Nl32;
         const uint32_t de = d;
@@ -1717,7 +1694,7 @@ __global__ __launch_bounds__(kTileThreads) void xd_apply_kernel(XdGeom g, XdBufs
       po[i] = o < G ? b.roff[(size_t)s * G + o] : 0u;
     }
     __syncthreads();
-    if (do_push) push_walk<kXbVZ, 0>(g.r, b.rb, X, acc, wmask, wlist, split ? nwav / 2 : 0u);
+    if (do_push) push_walk<kXbVZ, RecLayout::Ids32>(g.r, b.rb, X, acc, wmask, wlist, split ? nwav / 2 : 0u);
     if (do_pull) {  // replies, in send order: region s's items are G runs (one per owner)
       const uint32_t qtid = tid - qt0;
       for (uint32_t s = s0; s < s1; ++s) {

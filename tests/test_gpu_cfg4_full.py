@@ -7,7 +7,8 @@ final state:
     protocol on one device (device copies stand in for the RCCL collectives; the 8-GPU
     node runs the same engine calls over RCCL: gossip_hip.sharded), for the auto, sparse,
     dense (state all-gather) and exchange round plans;
-  * one engine holding all 2^27 nodes (the binned path past 4096 tiles, binned.hip V = 3);
+  * one engine holding all 2^27 nodes (the binned path past 4096 tiles: binned.hip, the one-shard
+    emit with big regions and the peers kept in LDS);
   * the OpenMP oracle (oracle/gossip_oracle.c) at 2^27.
 Reference: (*NodeState).Gossip, main.go:65-89, restated as rounds."""
 import os

@@ -9,7 +9,7 @@ regions; here are the shapes where the per-lane id count is irregular:
   pushpull-k1-R64   a region holds at most 16384 records: half the per-lane slots are empty
   pull-k2-R1        for many rounds almost every sender is empty: regions of 0 to a few hundred
                     records, totals that are no multiple of 1024, lanes without any id
-  push-k2-R64-loss  the fault path (V = 4 with k <= 2), records missing at random
+  push-k2-R64-loss  the fault path (peers redrawn, also with k <= 2), records missing at random
 
 Every round runs on the dense pipeline (sparse_frac -1) at N = 2^25 + 4099 (big regions, a ragged
 last region) and must equal the oracle bit for bit: per-round stats, per-rumor counts and the

@@ -3,7 +3,8 @@ OpenMP oracle.
 
 Past 4096 tiles the sender values no longer fit the emit's LDS beside the tile counters, so the
 dense emit bins 16384-sender regions with 16-bit packed tile counters and writes each push packed
-with its id (binned.hip V = 5; V = 4 with faults), and serve / apply run their per-XCD tile queues.
+with its id (binned.hip: the one-shard big-region emit, peers kept in LDS, redrawn with faults),
+and serve / apply run their per-XCD tile queues.
 N = 2^26 + 4099: 4097 tiles, a ragged last region and a ragged last tile.  Every path must equal the
 oracle bit for bit: per-round stats, per-rumor counts and the final state.  (Round 6 ran the same
 cases on the 32768-sender layout it measured and dropped, profiles/r06_huge/.)

@@ -160,13 +160,19 @@ def test_lockstep_dense_past_4096_tiles():
             e.close()
 
 
-@pytest.mark.parametrize("k,faults", [(3, {}), (2, dict(edge_loss=1 << 29, partitions=3))], ids=["k3", "k2-faults"])
-def test_lockstep_dense_past_4096_tiles_big_regions(k, faults):
+@pytest.mark.parametrize("N,G,k,faults", [((1 << 26) + 12345, 2, 3, {}),
+                                          ((1 << 26) + 12345, 2, 2, dict(edge_loss=1 << 29, partitions=3)),
+                                          (400009, 5, 3, dict(edge_loss=1 << 29, partitions=3))],
+                         ids=["k3", "k2-faults", "small-k3-faults"])
+def test_lockstep_dense_past_4096_tiles_big_regions(N, G, k, faults):
     """Past 4096 image tiles the sharded dense round's passes take 16384-sender regions
-    (make_sb_geom; binned.hip emit V = 6, 7 with redrawn peers for k > 2 or faults; k <= 2
-    without faults keeps them, V = 8, 9: test_lockstep_dense_past_4096_tiles).  Two ragged shards
-    on the state all-gather, every round dense, against one engine."""
-    N, R, G = (1 << 26) + 12345, 64, 2
+    (make_sb_geom; binned.hip: the sharded push and pull passes with big regions, peers redrawn
+    for k > 2 or faults; k <= 2 without faults keeps them in LDS:
+    test_lockstep_dense_past_4096_tiles).  Two ragged shards on the state all-gather, every round
+    dense, against one engine.  small-k3-faults: the same passes with small regions and peers
+    redrawn under faults, which no other test launches (k <= 2 keeps the peers in registers), on
+    five ragged shards."""
+    R = 64
     ref = Engine(N, R, "pushpull", k, 0x5EED0007, flags=1, **faults)
     ref.inject_random()
     want = ref.step(6)
