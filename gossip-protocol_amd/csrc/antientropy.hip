@@ -545,15 +545,16 @@ __global__ __launch_bounds__(kAeBinThreads, (NT > kAeBinTiles ? 4 : kAeEmitWaves
       // the round's churn (ae_churn_kernel's work, fused): a wave holds one 64-node chunk
       const uint64_t n = base + q * kAeBinThreads + tid;
       const uint64_t ch = n >> 6;
-      const bool in = n < a.N;
-      const uint64_t aw = in ? a.ab[2 * ch] : 0ull, sw = in ? a.ab[2 * ch + 1] : 0ull;
+      // cin: the chunk has a node (N = 64 c + 1: its lane 1 has none, and still carries the stale word)
+      const bool in = n < a.N, cin = (ch << 6) < a.N;
+      const uint64_t aw = in ? a.ab[2 * ch] : 0ull, sw = cin ? a.ab[2 * ch + 1] : 0ull;
       // one cipher for the churn and the first peers (k <= 3)
       u32x4 x = ae_first_draw((uint32_t)n, a.t, a.k, a.key0, a.key1);
       const bool al =
           in && churned((aw >> lane) & 1ull, ae_churn_word(x, (uint32_t)n, a.t, a.k, a.key0, a.key1), a.fail, a.rec);
       const uint64_t nb = __ballot(al);
       if (in && lane == 0) a.abn[2 * ch] = nb;
-      if (in && lane == 1) a.abn[2 * ch + 1] = sw;  // stale bits of S_t carried
+      if (cin && lane == 1) a.abn[2 * ch + 1] = sw;  // stale bits of S_t carried
       if (!al) continue;
       live |= 1u << q;
       stl |= (uint32_t)((sw >> lane) & 1ull) << q;
