@@ -131,15 +131,19 @@ typedef struct gossip_config {
   uint32_t churn_recover; /* ANTIENTROPY: P(dead -> alive) per round, as x / 2^32      */
   uint32_t edge_loss;   /* random modes, FLOOD and ANTIENTROPY: P(an edge's exchange is lost)
                            per round, x / 2^32 (the reference's lossy SyncRPC,
-                           main.go:77-87).  ANTIENTROPY (§2.11): a lost exchange moves neither
-                           end's row and is not counted in stats.messages; the same over the
-                           rows of GOSSIP_FLAG_AE_TOPO_PEERS (§2.12)                      */
+                           main.go:77-87): lost iff the edge's Philox draw is below x, so
+                           2^32 - 1 loses all but a draw of 0xFFFFFFFF.  ANTIENTROPY (§2.11): a
+                           lost exchange moves neither end's row and is not counted in
+                           stats.messages; the same over the rows of GOSSIP_FLAG_AE_TOPO_PEERS
+                           (§2.12)                                                        */
   uint32_t partitions;  /* random modes, FLOOD and ANTIENTROPY: 0/1 = none, P > 1 = nodes split
                            into P contiguous blocks that cannot reach each other.  ANTIENTROPY:
                            the target stays the max over all nodes, so a run does not converge
                            while a partition stands (gossip_step returns after max_rounds);
                            GOSSIP_FLAG_AE_TOPO_PEERS: a row's entries in other blocks are
-                           still drawn, and those exchanges are lost                       */
+                           still drawn, and those exchanges are lost.  Every u32 is taken:
+                           block(n) = n * P / N in 64 bits, so from P = N on each node is a
+                           block of its own (some blocks empty) and no exchange gets through */
   uint32_t stall_rounds; /* 0 = off.  D > 0: the reference's deadline stall (DESIGN.md §2.9,
                            main.go:72-87: one 2 s context per neighbour, retried forever
                            once it expired).  FLOOD: a node forwards each value down its

@@ -141,14 +141,14 @@ def build_state(engine, run):
         b(engine, R)
 
 
-def make_engines(factory, run, G, flags=0, params=None):
+def make_engines(factory, run, G, flags=0, params=None, seed=SEED):
     """G shard engines (G = 1: one engine) of a run, built; factory: Engine or op.OracleEngine."""
     _, mode, k, loss, parts = run
     N, R = run_shape(run)
     if G == 1:
-        engines = [factory(N, R, mode, k, SEED, flags=1 | flags, edge_loss=loss, partitions=parts)]
+        engines = [factory(N, R, mode, k, seed, flags=1 | flags, edge_loss=loss, partitions=parts)]
     else:
-        engines = [factory(N, R, mode, k, SEED, flags=1 | flags, shard_rank=r, shard_count=G, edge_loss=loss,
+        engines = [factory(N, R, mode, k, seed, flags=1 | flags, shard_rank=r, shard_count=G, edge_loss=loss,
                            partitions=parts, params=params) for r in range(G)]
     for e in engines:
         build_state(e, run)
@@ -161,8 +161,8 @@ def close_all(engines):
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(run):
-    (ref,) = make_engines(op.OracleEngine, run, 1)
+def _reference(run, seed=SEED):
+    (ref,) = make_engines(op.OracleEngine, run, 1, seed=seed)
     states, stats, infected = [ref.read_shard()[0].copy()], [], []
     for _ in range(64):
         res = ref.step(1)
@@ -173,20 +173,20 @@ def _reference(run):
             break
     for s in states + infected:
         s.setflags(write=False)
-    assert len(stats) == ROUNDS.get(run, len(stats))
+    assert seed != SEED or len(stats) == ROUNDS.get(run, len(stats))
     return tuple(states), tuple(stats), tuple(infected)
 
 
-def reference(run):
+def reference(run, seed=SEED):
     """One oracle engine over a run, a round at a time until it converges (at most 64 rounds):
     (S_0 .. S_T as read-only [N] uint64 arrays, the per-round stats).  Computed once, shared."""
-    return _reference(run)[:2]
+    return _reference(run, seed)[:2]
 
 
-def reference_infected(run):
+def reference_infected(run, seed=SEED):
     """The same run's per-rumor node counts after every round ([R] uint64 each), as gossip_step and
     gossip_group_step hand them out beside the stats."""
-    return _reference(run)[2]
+    return _reference(run, seed)[2]
 
 
 # -- the carousel -----------------------------------------------------------------------------
@@ -471,11 +471,11 @@ class GroupDriver:
         self.group.close()
 
 
-def open_driver(driver, factory, run, G, flags=0, params=None, **kw):
+def open_driver(driver, factory, run, G, flags=0, params=None, seed=SEED, **kw):
     """The driver (None: LockstepDriver) over the G shards of a run, built."""
     _, mode, k, loss, parts = run
     N, R = run_shape(run)
-    d = (driver or LockstepDriver)(factory, N, R, mode, k, SEED, G, flags=1 | flags, params=params, edge_loss=loss,
+    d = (driver or LockstepDriver)(factory, N, R, mode, k, seed, G, flags=1 | flags, params=params, edge_loss=loss,
                                    partitions=parts, **kw)
     try:
         for e in d.engines:
@@ -796,12 +796,12 @@ def check_round_wire(kind, log, S, run, G, t, knobs):
 
 # -- test bodies shared by the CPU file (factory = op.OracleEngine) and the GPU files (Engine) ------
 
-def body_carousel(factory, run, G, offset, table=SLOTS, flags=0, driver=None):
+def body_carousel(factory, run, G, offset, table=SLOTS, flags=0, driver=None, seed=SEED):
     """Per-round stats (and per-rumor counts where the driver has them), the kind sequence exactly as
     the table gives it, every shard's final state."""
-    states, want = reference(run)
-    infected = reference_infected(run)
-    d = open_driver(driver, factory, run, G, flags)
+    states, want = reference(run, seed)
+    infected = reference_infected(run, seed)
+    d = open_driver(driver, factory, run, G, flags, seed=seed)
     try:
         stats, kinds = carousel(d, table, offset, len(want),
                                 after_round=lambda i, kind, knobs: assert_infected(d, infected[i]))
