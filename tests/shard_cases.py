@@ -9,6 +9,8 @@ of states.py and ae_cases.py: tables and helpers, no tests.
                      is a function of the table and of what ran before it (expected_kinds);
   RUNS / PHILOX      the carousel runs, taken from test_state_builders.ROUNDS (hand-built states of
                      N0 nodes) plus one Philox run with shards of more than one 16384-node tile;
+  SHAPES / register  runs of any other shape: a run whose first field is registered names its own
+                     (N, R) and builder (tests/shard_sizes.py: shard edges on and beside the units);
   LockstepDriver, GroupDriver, OrderedDevDriver
                      who runs a round: sharded._round with the copy comm, gossip_group_step, or
                      sharded._round with OrderedDevComm (every copy a torch op on the engines' stream,
@@ -128,13 +130,29 @@ def run_id(run):
     return "-".join(str(x) for x in run)
 
 
+# runs that name their own shape and builder (tests/shard_sizes.py): run[0] -> (N, R, build(engine))
+SHAPES = {}
+
+
+def register(name, N, R, build):
+    """Makes `name` the first field of runs of N nodes and R rumors whose state is build(engine); the
+    name must say everything the state depends on, since reference() is cached by the run."""
+    assert name != "philox" and name not in st.BUILDERS and SHAPES.get(name, (N, R))[:2] == (N, R)
+    SHAPES[name] = (N, R, build)
+    return name
+
+
 def run_shape(run):
     """(N, R) of a run"""
+    if run[0] in SHAPES:
+        return SHAPES[run[0]][:2]
     return (PHILOX_N, 64) if run[0] == "philox" else (N0, st.BUILDERS[run[0]][1])
 
 
 def build_state(engine, run):
-    if run[0] == "philox":
+    if run[0] in SHAPES:
+        SHAPES[run[0]][2](engine)
+    elif run[0] == "philox":
         engine.inject_random()
     else:
         b, R = st.BUILDERS[run[0]]
