@@ -30,6 +30,7 @@
 #include <immintrin.h>
 #include "kernels.h"
 #include "monger.h"
+#include "monger_pull.h"
 #include "multi.h"
 #include "philox.h"
 #include "topo_peers.h"
@@ -108,6 +109,14 @@ struct gossip_engine {
   // counters: four bit planes [4][W][N], held from the first limit above 1 on
   uint32_t limit = 1;  // gossip_set_monger_limit
   DevBuf<uint64_t> counts;
+  // GOSSIP_FLAG_MONGER_PULL: hot, hot_next, counts and the three knobs as above; the
+  // servers' feedback of one round [W][N] each (all zero between rounds), and for W > 1 the bitmap
+  // of the nodes with something hot in H_t (mp_map_ok: it describes hot; an inject voids it)
+  bool monger_pull = false;
+  DevBuf<uint64_t> mp_need, mp_less, mp_map;
+  bool mp_map_ok = true;
+  uint64_t mp_hot_nodes = 0;  // nodes with something hot after the last round (the stop rule)
+  bool mongering() const { return monger || monger_pull; }
   // stall mode, random modes: streak per node, all N nodes on every shard
   DevBuf<uint8_t> stall_d;
   // FLOOD with faults, one shard: per out-edge pending values and first senders
@@ -1221,8 +1230,23 @@ int compute_round(gossip_engine* e, const uint64_t* gathered) {
     e->sx_valid = true;  // totals of the own nodes and exact bitmaps of S_{t+1}, fused into the apply pass
     return GOSSIP_OK;
   } else {
+    if (e->mp_map && !e->mp_map_ok) {  // pull mongering, W > 1, after an inject: the bitmap of H_t again (outside timer 0)
+      HIP_OK(e, launch_monger_hot_scan(e->hot, e->N, e->W, e->mp_map, nullptr, e->stream));
+      e->mp_map_ok = true;
+    }
     // timer 0 covers the whole S_t -> S_{t+1} transform (seed copy + round kernel)
     if ((rc = timer_begin(e, 0))) return rc;
+    if (e->monger_pull) {  // pull mongering: request pass (writes both next images whole), close pass
+      uint64_t* hot_nodes = e->partial_d + 4 + e->R;  // (the internal slot after infected[R], zeroed with the partials)
+      const MongerPullArgs m{a,       e->hot,  e->hot_next,   e->mp_need, e->mp_less, e->mp_map, hot_nodes,
+                             e->cool, e->blind, e->topo_peers, e->counts,  e->limit};
+      HIP_OK(e, launch_round_monger_pull(m, e->stream));
+      HIP_OK(e, launch_monger_pull_close(m, e->stream));
+      if ((rc = timer_end(e, 0))) return rc;
+      if ((rc = timer_begin(e, 1))) return rc;
+      HIP_OK(e, launch_stats(a, e->stream));
+      return timer_end(e, 1);
+    }
     HIP_OK(e, hipMemcpyAsync(e->Snext, e->S, bytes, hipMemcpyDeviceToDevice, e->stream));
     if (e->monger) {  // rumor mongering: H moves with S
       HIP_OK(e, hipMemcpyAsync(e->hot_next, e->hot, bytes, hipMemcpyDeviceToDevice, e->stream));
@@ -1259,7 +1283,7 @@ void rotate(gossip_engine* e) {
   } else if (!e->binned) {  // binned rounds run in place
     e->cur ^= 1;
     bind_slices(e);
-    if (e->monger) e->hot.swap(e->hot_next);
+    if (e->mongering()) e->hot.swap(e->hot_next);
   }
 }
 
@@ -1393,6 +1417,13 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
                      "FLOOD sends to the whole row)";
     return GOSSIP_EINVAL;
   }
+  // (before the PUSH-only check of bit 8: both bits together are refused in the new flag's name)
+  if ((cfg->flags & GOSSIP_FLAG_MONGER_PULL) &&
+      (cfg->mode != GOSSIP_MODE_PULL || (cfg->flags & GOSSIP_FLAG_MONGER))) {
+    g_create_error = "GOSSIP_FLAG_MONGER_PULL applies to PULL, without GOSSIP_FLAG_MONGER (hot nodes answer pulls; "
+                     "DESIGN.md §2.15)";
+    return GOSSIP_EINVAL;
+  }
   if ((cfg->flags & GOSSIP_FLAG_MONGER) && cfg->mode != GOSSIP_MODE_PUSH) {
     g_create_error = "GOSSIP_FLAG_MONGER applies to PUSH (rumor mongering pushes the hot rumors; DESIGN.md §2.13)";
     return GOSSIP_EINVAL;
@@ -1408,6 +1439,10 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
   }
   if ((cfg->flags & GOSSIP_FLAG_MONGER) && (cfg->stall_rounds || G > 1)) {
     g_create_error = "GOSSIP_FLAG_MONGER runs on one shard and without stall_rounds (DESIGN.md §2.13)";
+    return GOSSIP_ENOTSUP;
+  }
+  if ((cfg->flags & GOSSIP_FLAG_MONGER_PULL) && (cfg->stall_rounds || G > 1)) {
+    g_create_error = "GOSSIP_FLAG_MONGER_PULL runs on one shard and without stall_rounds (DESIGN.md §2.15)";
     return GOSSIP_ENOTSUP;
   }
   const bool faulty = cfg->edge_loss || cfg->partitions > 1 || cfg->stall_rounds;
@@ -1465,8 +1500,9 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
   e->topo_peers = (cfg->flags & GOSSIP_FLAG_TOPO_PEERS) != 0;
   e->ae_topo = (cfg->flags & GOSSIP_FLAG_AE_TOPO_PEERS) != 0;
   e->monger = (cfg->flags & GOSSIP_FLAG_MONGER) != 0;
+  e->monger_pull = (cfg->flags & GOSSIP_FLAG_MONGER_PULL) != 0;
   // such engines run the direct kernels: never binned, no sparse-sharded or exchange state
-  const uint32_t direct_flags = GOSSIP_FLAG_DIRECT | GOSSIP_FLAG_TOPO_PEERS | GOSSIP_FLAG_MONGER;
+  const uint32_t direct_flags = GOSSIP_FLAG_DIRECT | GOSSIP_FLAG_TOPO_PEERS | GOSSIP_FLAG_MONGER | GOSSIP_FLAG_MONGER_PULL;
   e->fw.D = cfg->stall_rounds;
 
   auto bail = [&](int rc) {
@@ -1563,7 +1599,10 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
   } else if (!alloc(e->img[0], image / 8) || !alloc(e->img[1], image / 8)) {
     return bail(GOSSIP_ENOMEM);
   }
-  if (e->monger && (!alloc(e->hot, shard / 8) || !alloc(e->hot_next, shard / 8))) return bail(GOSSIP_ENOMEM);
+  if (e->mongering() && (!alloc(e->hot, shard / 8) || !alloc(e->hot_next, shard / 8))) return bail(GOSSIP_ENOMEM);
+  if (e->monger_pull && (!alloc(e->mp_need, shard / 8) || !alloc(e->mp_less, shard / 8) ||
+                         (e->W > 1 && !alloc(e->mp_map, (e->N + 63) / 64))))
+    return bail(GOSSIP_ENOMEM);
   bind_slices(e);
   if (e->mode != GOSSIP_MODE_FLOOD && e->mode != GOSSIP_MODE_ANTIENTROPY && !(cfg->flags & direct_flags) &&
       bin_path_ok(e->N, e->k, e->W, G)) {
@@ -1844,7 +1883,10 @@ int gossip_reset(gossip_engine_t* e) {
     // binned single-shard rounds run in place on S and never read the other image
     HIP_OK(e, hipMemsetAsync(e->S, 0, shard, e->stream));
     if (!e->binned) HIP_OK(e, hipMemsetAsync(e->Snext, 0, shard, e->stream));
-    if (e->monger) {  // (cool and blind stay)
+    if (e->mongering()) {  // (cool and blind stay; the pull feedback buffers are zero between rounds)
+      if (e->mp_map) HIP_OK(e, hipMemsetAsync(e->mp_map, 0, (e->N + 63) / 64 * 8, e->stream));
+      e->mp_map_ok = true;
+      e->mp_hot_nodes = 0;
       HIP_OK(e, hipMemsetAsync(e->hot, 0, shard, e->stream));
       HIP_OK(e, hipMemsetAsync(e->hot_next, 0, shard, e->stream));
       if (e->counts) HIP_OK(e, hipMemsetAsync(e->counts, 0, 4 * shard, e->stream));  // (the limit stays)
@@ -1895,7 +1937,8 @@ int gossip_inject(gossip_engine_t* e, uint64_t node, uint32_t rumor) {
                                      e->cfg.flags, e->stream));
     return GOSSIP_OK;
   }
-  if (e->monger) {  // hot where it is new; a held rumor, cooled or not, stays as it is
+  if (e->mongering()) {  // hot where it is new; a held rumor, cooled or not, stays as it is
+    e->mp_map_ok = false;
     HIP_OK(e, launch_monger_inject(e->S, e->hot, e->N, e->R, e->key0, e->key1, (int64_t)node, rumor, e->stream));
     return GOSSIP_OK;
   }
@@ -1925,7 +1968,8 @@ int gossip_inject_random(gossip_engine_t* e) {
                                      e->stream));
     return GOSSIP_OK;
   }
-  if (e->monger) {
+  if (e->mongering()) {
+    e->mp_map_ok = false;
     HIP_OK(e, launch_monger_inject(e->S, e->hot, e->N, e->R, e->key0, e->key1, -1, 0, e->stream));
     return GOSSIP_OK;
   }
@@ -2010,6 +2054,10 @@ int gossip_round_compute(gossip_engine_t* e, uint64_t* partial) {
   }
   if (int rc = timer_collect(e)) return rc;
   std::memcpy(partial, e->partial_h, part_len(e) * 8);
+  if (e->monger_pull) {  // the close pass's count of hot nodes rode in the internal slot
+    e->mp_hot_nodes = partial[4 + e->R];
+    partial[4 + e->R] = 0;
+  }
   if (e->mode != GOSSIP_MODE_ANTIENTROPY) partial[1] = e->nown;
   else partial[3] = (e->cfg.flags & GOSSIP_FLAG_HASH) ? e->ae_hash : 0;
   e->last_sparse = false;
@@ -2618,7 +2666,8 @@ int gossip_ae_finish(gossip_engine_t* e, uint64_t* partial) {
 
 int gossip_set_monger(gossip_engine_t* e, uint32_t cool, uint32_t blind) {
   if (!e) return GOSSIP_EINVAL;
-  if (!e->monger) return e->fail(GOSSIP_ESTATE, "gossip_set_monger needs an engine created with GOSSIP_FLAG_MONGER");
+  if (!e->mongering())
+    return e->fail(GOSSIP_ESTATE, "gossip_set_monger needs an engine created with GOSSIP_FLAG_MONGER or _MONGER_PULL");
   if (blind > 1) return e->fail(GOSSIP_EINVAL, "blind must be 0 or 1");
   e->cool = cool;
   e->blind = blind;
@@ -2627,8 +2676,8 @@ int gossip_set_monger(gossip_engine_t* e, uint32_t cool, uint32_t blind) {
 
 int gossip_set_monger_limit(gossip_engine_t* e, uint32_t limit) {
   if (!e) return GOSSIP_EINVAL;
-  if (!e->monger)
-    return e->fail(GOSSIP_ESTATE, "gossip_set_monger_limit needs an engine created with GOSSIP_FLAG_MONGER");
+  if (!e->mongering())
+    return e->fail(GOSSIP_ESTATE, "gossip_set_monger_limit needs an engine created with GOSSIP_FLAG_MONGER or _MONGER_PULL");
   if (limit < 1 || limit > 15) return e->fail(GOSSIP_EINVAL, "limit must be in [1, 15]");
   if (limit > 1 && !e->counts) {  // counts are kept from here on: what cooled before reads 0
     if (int rc = set_dev(e)) return rc;
@@ -2727,6 +2776,13 @@ int gossip_step(gossip_engine_t* e, uint32_t max_rounds, gossip_round_stats_t* s
       if (st.messages == 0) break;
       continue;
     }
+    // pull mongering: until the first round that leaves no node hot (reported).  Not
+    // at messages == 0: a round in which nobody happens to pull from a hot node sends nothing while
+    // rumors are still hot
+    if (e->monger_pull) {
+      if (e->mp_hot_nodes == 0) break;
+      continue;
+    }
     // converged, or FLOOD quiescence: no message sent means S_{t+1} == S_t forever
     if (st.converged || (e->mode == GOSSIP_MODE_FLOOD && st.messages == 0)) break;
   }
@@ -2758,7 +2814,8 @@ int gossip_read_shard(gossip_engine_t* e, uint64_t* out, uint64_t n_words) {
 
 int gossip_read_hot_shard(gossip_engine_t* e, uint64_t* out, uint64_t n_words) {
   if (!e || !out) return GOSSIP_EINVAL;
-  if (!e->monger) return e->fail(GOSSIP_ESTATE, "gossip_read_hot_shard needs an engine created with GOSSIP_FLAG_MONGER");
+  if (!e->mongering())
+    return e->fail(GOSSIP_ESTATE, "gossip_read_hot_shard needs an engine created with GOSSIP_FLAG_MONGER or _MONGER_PULL");
   if (n_words < (uint64_t)e->W * e->nown) return e->fail(GOSSIP_EINVAL, "output too small");
   if (int rc = set_dev(e)) return rc;
   HIP_OK(e, hipStreamSynchronize(e->stream));
@@ -2769,8 +2826,8 @@ int gossip_read_hot_shard(gossip_engine_t* e, uint64_t* out, uint64_t n_words) {
 
 int gossip_read_monger_counts(gossip_engine_t* e, uint64_t* out, uint64_t n_words) {
   if (!e || !out) return GOSSIP_EINVAL;
-  if (!e->monger)
-    return e->fail(GOSSIP_ESTATE, "gossip_read_monger_counts needs an engine created with GOSSIP_FLAG_MONGER");
+  if (!e->mongering())
+    return e->fail(GOSSIP_ESTATE, "gossip_read_monger_counts needs an engine created with GOSSIP_FLAG_MONGER or _MONGER_PULL");
   const uint64_t plane = (uint64_t)e->W * e->nown;
   if (n_words != 4 * plane) return e->fail(GOSSIP_EINVAL, "n_words must be 4 * W * Nl_owned");
   if (!e->counts) {  // no limit above 1 yet: nothing was counted
@@ -2783,6 +2840,18 @@ int gossip_read_monger_counts(gossip_engine_t* e, uint64_t* out, uint64_t n_word
     for (uint32_t w = 0; w < e->W; ++w)
       HIP_OK(e, hipMemcpy(out + b * plane + (size_t)w * e->nown, e->counts + ((size_t)b * e->W + w) * e->Nl,
                           e->nown * 8, hipMemcpyDeviceToHost));
+  return GOSSIP_OK;
+}
+
+int gossip_monger_hot_nodes(gossip_engine_t* e, uint64_t* out) {
+  if (!e || !out) return GOSSIP_EINVAL;
+  if (!e->mongering())
+    return e->fail(GOSSIP_ESTATE, "gossip_monger_hot_nodes needs an engine created with GOSSIP_FLAG_MONGER or _MONGER_PULL");
+  if (int rc = set_dev(e)) return rc;
+  HIP_OK(e, hipMemsetAsync(e->scratch_d, 0, 8, e->stream));
+  HIP_OK(e, launch_monger_hot_scan(e->hot, e->N, e->W, nullptr, e->scratch_d, e->stream));
+  HIP_OK(e, hipStreamSynchronize(e->stream));
+  HIP_OK(e, hipMemcpy(out, e->scratch_d, 8, hipMemcpyDeviceToHost));
   return GOSSIP_OK;
 }
 

@@ -24,6 +24,7 @@
 // a register, a load or a launch (§2.14 item 9).
 #include "monger.h"
 
+#include "planes.h"
 #include "sender.h"
 
 namespace gossip {
@@ -43,37 +44,8 @@ __device__ __forceinline__ void draw_coins(const MongerArgs& m, uint32_t n, uint
 // The counters: C[n][r] in 0..15 as four bit planes in the layout of S
 // and H, so that one instruction updates 64 rumors.  Only lane n touches C[*][n]: plain loads and
 // stores.  The planes of a word are loaded before the batch's atomics are issued and are consumed
-// before them, as every other load of the batch.
+// before them, as every other load of the batch.  planes_add and planes_ge are in planes.h.
 // ---------------------------------------------------------------------------
-
-// c += 1 at the bits of x, saturating at 15: a ripple-carry add over the planes; a carry out of
-// plane 3 sets all four planes of those bits.
-__device__ __forceinline__ void planes_add(uint64_t (&c)[4], uint64_t x) {
-  uint64_t carry = x;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const uint64_t t = c[b] & carry;
-    c[b] ^= carry;
-    carry = t;
-  }
-#pragma unroll
-  for (int b = 0; b < 4; ++b) c[b] |= carry;
-}
-
-// The bits whose count is at least limit (uniform, 1..15), most significant plane first.
-__device__ __forceinline__ uint64_t planes_ge(const uint64_t (&c)[4], uint32_t limit) {
-  uint64_t gt = 0, eq = ~0ull;
-#pragma unroll
-  for (int b = 3; b >= 0; --b) {
-    if ((limit >> b) & 1u) {
-      eq &= c[b];
-    } else {
-      gt |= eq & c[b];
-      eq &= ~c[b];
-    }
-  }
-  return gt | eq;
-}
 
 // What one batch does to one word: h = that word of H_t[n] (not zero), woff = its offset in S and H.
 // Returns the counted bits of the edges whose coin holds; COUNT: and adds each such edge's set to

@@ -19,6 +19,7 @@ FLAG_AE_DIRECT_SCAN = 1 << 5
 FLAG_TOPO_PEERS = 1 << 6  # random modes: peers drawn from the node's topology row
 FLAG_AE_TOPO_PEERS = 1 << 7  # ANTIENTROPY: exchange peers drawn from the node's topology row
 FLAG_MONGER = 1 << 8  # PUSH: rumor mongering, nodes lose interest in what they push
+FLAG_MONGER_PULL = 1 << 9  # PULL: hot nodes answer pulls and cool by the pullers' feedback
 
 ABI_VERSION = 10  # include/gossip.h GOSSIP_ABI_VERSION (v10: gossip_round_wall)
 
@@ -120,6 +121,7 @@ SIGNATURES = [
     ("read_shard", C.c_int, [P, U64P, C.c_uint64]),
     ("read_hot_shard", C.c_int, [P, U64P, C.c_uint64]),
     ("read_monger_counts", C.c_int, [P, U64P, C.c_uint64]),
+    ("monger_hot_nodes", C.c_int, [P, U64P]),
     ("read_versions", C.c_int, [P, C.c_uint64, U32P, C.c_uint32, U32P]),
     ("shard_range", C.c_int, [P, U64P, U64P]),
     ("state_hash", C.c_int, [P, U64P]),
@@ -144,7 +146,7 @@ SIGNATURES = [
 # entry points of the HIP engine only (the oracle library exports the rest under "oracle_")
 ENGINE_ONLY = {"comm_unique_id", "comm_init_rank", "group_create", "group_destroy", "group_engine", "group_transport",
                "group_step", "group_last_error", "set_monger", "read_hot_shard", "set_monger_limit",
-               "read_monger_counts"}
+               "read_monger_counts", "monger_hot_nodes"}
 
 
 def bind(lib: C.CDLL, prefix: str, names=None) -> C.CDLL:

@@ -470,7 +470,9 @@ class Engine(AbiEngine):
     def set_monger(self, cool, blind: bool = False):
         """FLAG_MONGER, for the rounds that follow: cool = the chance that a counted
         contact makes the sender lose interest, a probability (float, turned into x / 2^32 by
-        loss_threshold) or the u32 threshold itself (int); blind: every attempt counts, else feedback."""
+        loss_threshold) or the u32 threshold itself (int); blind: every attempt counts, else feedback.
+        FLAG_MONGER_PULL (§2.15): the chance that a round's needless pulls count at the server; blind:
+        every delivered request counts every hot rumor as needless."""
         x = loss_threshold(cool) if isinstance(cool, float) else int(cool)
         self._check(self._fn("set_monger")(self._h, C.c_uint32(x), C.c_uint32(int(blind))))
 
@@ -499,6 +501,13 @@ class Engine(AbiEngine):
             for b in range(4):
                 out[r] |= ((planes[b, r // 64] >> np.uint64(r % 64)) & np.uint64(1)).astype(np.uint8) << b
         return out
+
+    def hot_nodes(self) -> int:
+        """FLAG_MONGER and FLAG_MONGER_PULL: the nodes that hold a hot rumor in the current state (a
+        FLAG_MONGER_PULL step ends with the first round that leaves none)."""
+        out = C.c_uint64()
+        self._check(self._fn("monger_hot_nodes")(self._h, C.byref(out)))
+        return out.value
 
     def kernel_time(self, which: int):
         ms, n = C.c_double(), C.c_uint64()

@@ -77,6 +77,11 @@ const (
 	// still hot on and loses interest by SetMonger's coin; Step runs until a round sends nothing,
 	// and RoundStats.Messages counts k per node that pushed.
 	FlagMonger Flags = Flags(C.GOSSIP_FLAG_MONGER)
+	// FlagMongerPull: Pull as rumor mongering (DESIGN.md §2.15): every node asks k peers, a peer
+	// answers with the rumors it is still hot on and loses interest by what the round's requests
+	// told it (SetMonger, SetMongerLimit); Step runs until a round leaves no node hot (HotNodes),
+	// and RoundStats.Messages counts the replies that carried a rumor.
+	FlagMongerPull Flags = Flags(C.GOSSIP_FLAG_MONGER_PULL)
 )
 
 // Config mirrors gossip_config_t.  Probabilities are thresholds x / 2^32 (Threshold).
@@ -523,6 +528,18 @@ func (e *Engine) ReadMongerCounts() ([]uint64, error) {
 		return nil, e.fail(rc)
 	}
 	return out, nil
+}
+
+// HotNodes returns the number of nodes that hold a hot rumor in the current state (FlagMonger,
+// FlagMongerPull).
+func (e *Engine) HotNodes() (uint64, error) {
+	e.mu.Lock()
+	defer e.mu.Unlock()
+	var out C.uint64_t
+	if rc := C.gossip_monger_hot_nodes(e.h, &out); rc != 0 {
+		return 0, e.fail(rc)
+	}
+	return uint64(out), nil
 }
 
 // ReadVersions returns one node's K versions and its alive flag (ANTIENTROPY).

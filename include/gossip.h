@@ -95,7 +95,7 @@ enum gossip_flags {
                                           direct sparse scan (as "ae_dense_bin" 0 with
                                           GOSSIP_FLAG_AE_DIRECT_SCAN).  With any other mode, or together
                                           with GOSSIP_FLAG_TOPO_PEERS, gossip_create returns GOSSIP_EINVAL */
-  GOSSIP_FLAG_MONGER = 1u << 8         /* PUSH: rumor mongering.  Beside the rumors a node
+  GOSSIP_FLAG_MONGER = 1u << 8,        /* PUSH: rumor mongering.  Beside the rumors a node
                                           knows the engine keeps the ones it is still spreading ("hot",
                                           gossip_read_hot_shard): a rumor is hot where it is new, a push
                                           carries only the hot rumors, and a counted contact makes the
@@ -114,6 +114,29 @@ enum gossip_flags {
                                           gossip_set_monger_limit adds the counter rule:
                                           a rumor cools only once `limit` of its counted contacts have
                                           passed the coin; the counts are read by gossip_read_monger_counts */
+  GOSSIP_FLAG_MONGER_PULL = 1u << 9    /* PULL: pull rumor mongering.  The engine keeps the
+                                          known and the hot rumors as a GOSSIP_FLAG_MONGER engine does.  Every
+                                          node (with GOSSIP_FLAG_TOPO_PEERS: every node with a row) sends k
+                                          pull requests per round to the peers an unflagged PULL engine of
+                                          the same seed draws, a full node too; a request lost by edge_loss
+                                          or partitions reaches nobody.  A delivered request is answered with
+                                          the server's hot rumors, hot at the requester where they are new.
+                                          The node that loses interest is the server, once per round and
+                                          rumor from all the requests that reached it: a rumor some requester
+                                          lacked has its count set back to 0 and stays; else, if some
+                                          requester held it and the server's coin (one per node and round,
+                                          Philox stream tag 5) is below cool, its count goes up by one and
+                                          it cools at `limit` (gossip_set_monger, gossip_set_monger_limit;
+                                          blind = 1: every delivered request counts every hot rumor as held).
+                                          stats.messages counts the delivered requests whose server had
+                                          something hot.  gossip_step runs until the first round that leaves
+                                          no node hot (reported), not until converged and not until a round
+                                          sends nothing.  With cool = 0 (the value after create) the engine
+                                          equals an unflagged PULL engine bit for bit.  Composes with
+                                          GOSSIP_FLAG_TOPO_PEERS, _HASH and _TIMING and with edge_loss /
+                                          partitions; _DIRECT and _DENSE change nothing.  With any mode but
+                                          PULL, or together with GOSSIP_FLAG_MONGER, gossip_create returns
+                                          GOSSIP_EINVAL, with stall_rounds or shard_count > 1 GOSSIP_ENOTSUP */
 };
 
 typedef struct gossip_config {
@@ -169,7 +192,11 @@ typedef struct gossip_round_stats {
                            and not stalled (PUSH: and a rumor to send);
                            GOSSIP_FLAG_MONGER: k per node that holds a hot rumor (and, with
                            GOSSIP_FLAG_TOPO_PEERS, has a row), lost attempts included
-                           (DESIGN.md §2.13); other random-mode engines: 0           */
+                           (DESIGN.md §2.13);
+                           GOSSIP_FLAG_MONGER_PULL: the delivered pull requests whose server had
+                           something hot, the replies that carried a rumor; an exchange with oneself
+                           over a self-loop included;
+                           other random-mode engines: 0                              */
   uint64_t state_hash;  /* GOSSIP_FLAG_HASH: Σ mix64 over nonzero words, else 0   */
 } gossip_round_stats_t;
 
@@ -262,13 +289,13 @@ int gossip_set_param(gossip_engine_t* eng, const char* name, double value);
 int gossip_set_topology_csr(gossip_engine_t* eng, const uint32_t* row_ptr, const uint32_t* col,
                             uint64_t n, uint64_t n_edges);
 
-/* Clears every rumor bit (GOSSIP_FLAG_MONGER: the hot bits and the counts too; cool, blind and the
+/* Clears every rumor bit (GOSSIP_FLAG_MONGER and _MONGER_PULL: the hot bits and the counts too; cool, blind and the
  * limit stay) and sets t = 0. */
 int gossip_reset(gossip_engine_t* eng);
 
 /* Client broadcast of rumor slot `rumor` to `node` (no-op when the node is
  * outside this shard or already holds it — the dedupe of main.go:113).
- * GOSSIP_FLAG_MONGER: the rumor is hot at a node it is new at; one the node holds
+ * GOSSIP_FLAG_MONGER and _MONGER_PULL: the rumor is hot at a node it is new at; one the node holds
  * already, cooled or not, stays as it is, and so does its count (gossip_inject_random likewise).
  * ANTIENTROPY: a local write of key `rumor` at `node` (its version + 1). */
 int gossip_inject(gossip_engine_t* eng, uint64_t node, uint32_t rumor);
@@ -302,13 +329,17 @@ int gossip_set_monger(gossip_engine_t* eng, uint32_t cool, uint32_t blind);
  * call with limit > 1 on (that call allocates them, zeroed: a rumor that cooled earlier reads 0), also
  * after the limit is set back to 1; a lowered limit cools a hot rumor at its next counted contact whose
  * coin holds, not before.  GOSSIP_ESTATE on an engine created without the flag, GOSSIP_EINVAL for 0 or
- * more than 15, GOSSIP_ENOMEM when the counts cannot be allocated (engine and limit then unchanged). */
+ * more than 15, GOSSIP_ENOMEM when the counts cannot be allocated (engine and limit then unchanged).
+ * GOSSIP_FLAG_MONGER_PULL takes both calls too: there the counts are the server's, a round
+ * adds at most one to a count, and a pull that needed the rumor sets it back to 0. */
 int gossip_set_monger_limit(gossip_engine_t* eng, uint32_t limit);
 
 /* Runs rounds until converged (FLOOD also: a round that sends nothing) or max_rounds
  * rounds have run.  GOSSIP_FLAG_MONGER: until the first round that sends nothing (that round is
  * reported) or max_rounds, and not until converged; on return gossip_round_index and the state
- * are those of the last reported round.  stats: max_rounds entries or NULL; infected: max_rounds * R
+ * are those of the last reported round.  GOSSIP_FLAG_MONGER_PULL: until the first round that leaves no
+ * node hot (reported; gossip_monger_hot_nodes is then 0) or max_rounds — a round that sends nothing
+ * while rumors are hot does not end the run.  stats: max_rounds entries or NULL; infected: max_rounds * R
  * counters (row t = per-rumor infected counts after round t) or NULL.
  * G > 1: the engine needs its collectives first (gossip_comm_init_rank below); every
  * rank calls gossip_step with the same max_rounds and gets the same global stats. */
@@ -361,6 +392,13 @@ int gossip_read_hot_shard(gossip_engine_t* eng, uint64_t* out, uint64_t n_words)
  * out[(b * W + w) * Nl_owned + i]; n_words must be 4 * W * Nl_owned (else GOSSIP_EINVAL).  All zero
  * while no limit above 1 was ever set.  GOSSIP_ESTATE on an engine created without the flag. */
 int gossip_read_monger_counts(gossip_engine_t* eng, uint64_t* out, uint64_t n_words);
+/* GOSSIP_FLAG_MONGER and _MONGER_PULL: the number of nodes that hold a hot rumor in the current state
+ * (after gossip_step on a GOSSIP_FLAG_MONGER_PULL engine: 0 unless max_rounds ended the run).
+ * gossip_read_hot_shard and gossip_read_monger_counts work on both flags alike.  A host that runs
+ * the gossip_round_* calls itself instead of gossip_step applies GOSSIP_FLAG_MONGER_PULL's stop rule
+ * with this call: the partial vector does not carry the number.  GOSSIP_ESTATE on an engine created
+ * with neither flag, GOSSIP_EINVAL for a null argument. */
+int gossip_monger_hot_nodes(gossip_engine_t* eng, uint64_t* out);
 /* ANTIENTROPY readout: the K versions of one node (owned by this shard), and its alive flag. */
 int gossip_read_versions(gossip_engine_t* eng, uint64_t node, uint32_t* out, uint32_t ncomp, uint32_t* alive);
 /* ANTIENTROPY readout of every owned row: out[i * K + c] for owned node lo + i. */
