@@ -31,6 +31,7 @@
 #include "kernels.h"
 #include "monger.h"
 #include "monger_pull.h"
+#include "monger_pushpull.h"
 #include "multi.h"
 #include "philox.h"
 #include "topo_peers.h"
@@ -116,7 +117,12 @@ struct gossip_engine {
   DevBuf<uint64_t> mp_need, mp_less, mp_map;
   bool mp_map_ok = true;
   uint64_t mp_hot_nodes = 0;  // nodes with something hot after the last round (the stop rule)
-  bool mongering() const { return monger || monger_pull; }
+  // GOSSIP_FLAG_MONGER_PUSHPULL: everything a GOSSIP_FLAG_MONGER_PULL engine holds, and the
+  // gains of one round [W][N] (all zero between rounds: no reset or inject touches them)
+  bool monger_pushpull = false;
+  DevBuf<uint64_t> pp_gain;
+  bool mongering() const { return monger || monger_pull || monger_pushpull; }
+  bool hot_stop() const { return monger_pull || monger_pushpull; }  // the run ends when no node is hot
   // stall mode, random modes: streak per node, all N nodes on every shard
   DevBuf<uint8_t> stall_d;
   // FLOOD with faults, one shard: per out-edge pending values and first senders
@@ -1230,12 +1236,24 @@ int compute_round(gossip_engine* e, const uint64_t* gathered) {
     e->sx_valid = true;  // totals of the own nodes and exact bitmaps of S_{t+1}, fused into the apply pass
     return GOSSIP_OK;
   } else {
-    if (e->mp_map && !e->mp_map_ok) {  // pull mongering, W > 1, after an inject: the bitmap of H_t again (outside timer 0)
+    if (e->mp_map && !e->mp_map_ok) {  // pull and push-pull mongering, W > 1, after an inject: the bitmap of H_t again (outside timer 0)
       HIP_OK(e, launch_monger_hot_scan(e->hot, e->N, e->W, e->mp_map, nullptr, e->stream));
       e->mp_map_ok = true;
     }
     // timer 0 covers the whole S_t -> S_{t+1} transform (seed copy + round kernel)
     if ((rc = timer_begin(e, 0))) return rc;
+    if (e->monger_pushpull) {  // push-pull mongering: request pass (ORs only), close pass (writes both next images whole)
+      uint64_t* hot_nodes = e->partial_d + 4 + e->R;  // (the internal slot after infected[R], zeroed with the partials)
+      const MongerPushPullArgs x{{a,       e->hot,  e->hot_next,   e->mp_need, e->mp_less, e->mp_map, hot_nodes,
+                                  e->cool, e->blind, e->topo_peers, e->counts,  e->limit},
+                                 e->pp_gain};
+      HIP_OK(e, launch_round_monger_pushpull(x, e->stream));
+      HIP_OK(e, launch_monger_pushpull_close(x, e->stream));
+      if ((rc = timer_end(e, 0))) return rc;
+      if ((rc = timer_begin(e, 1))) return rc;
+      HIP_OK(e, launch_stats(a, e->stream));
+      return timer_end(e, 1);
+    }
     if (e->monger_pull) {  // pull mongering: request pass (writes both next images whole), close pass
       uint64_t* hot_nodes = e->partial_d + 4 + e->R;  // (the internal slot after infected[R], zeroed with the partials)
       const MongerPullArgs m{a,       e->hot,  e->hot_next,   e->mp_need, e->mp_less, e->mp_map, hot_nodes,
@@ -1417,6 +1435,13 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
                      "FLOOD sends to the whole row)";
     return GOSSIP_EINVAL;
   }
+  // (before the checks of bits 8 and 9: with either of them bit 10 is refused in its own name)
+  if ((cfg->flags & GOSSIP_FLAG_MONGER_PUSHPULL) &&
+      (cfg->mode != GOSSIP_MODE_PUSHPULL || (cfg->flags & (GOSSIP_FLAG_MONGER | GOSSIP_FLAG_MONGER_PULL)))) {
+    g_create_error = "GOSSIP_FLAG_MONGER_PUSHPULL applies to PUSHPULL, without GOSSIP_FLAG_MONGER or _MONGER_PULL (both "
+                     "ends of an exchange send their hot rumors; DESIGN.md §2.16)";
+    return GOSSIP_EINVAL;
+  }
   // (before the PUSH-only check of bit 8: both bits together are refused in the new flag's name)
   if ((cfg->flags & GOSSIP_FLAG_MONGER_PULL) &&
       (cfg->mode != GOSSIP_MODE_PULL || (cfg->flags & GOSSIP_FLAG_MONGER))) {
@@ -1443,6 +1468,10 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
   }
   if ((cfg->flags & GOSSIP_FLAG_MONGER_PULL) && (cfg->stall_rounds || G > 1)) {
     g_create_error = "GOSSIP_FLAG_MONGER_PULL runs on one shard and without stall_rounds (DESIGN.md §2.15)";
+    return GOSSIP_ENOTSUP;
+  }
+  if ((cfg->flags & GOSSIP_FLAG_MONGER_PUSHPULL) && (cfg->stall_rounds || G > 1)) {
+    g_create_error = "GOSSIP_FLAG_MONGER_PUSHPULL runs on one shard and without stall_rounds (DESIGN.md §2.16)";
     return GOSSIP_ENOTSUP;
   }
   const bool faulty = cfg->edge_loss || cfg->partitions > 1 || cfg->stall_rounds;
@@ -1501,8 +1530,10 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
   e->ae_topo = (cfg->flags & GOSSIP_FLAG_AE_TOPO_PEERS) != 0;
   e->monger = (cfg->flags & GOSSIP_FLAG_MONGER) != 0;
   e->monger_pull = (cfg->flags & GOSSIP_FLAG_MONGER_PULL) != 0;
+  e->monger_pushpull = (cfg->flags & GOSSIP_FLAG_MONGER_PUSHPULL) != 0;
   // such engines run the direct kernels: never binned, no sparse-sharded or exchange state
-  const uint32_t direct_flags = GOSSIP_FLAG_DIRECT | GOSSIP_FLAG_TOPO_PEERS | GOSSIP_FLAG_MONGER | GOSSIP_FLAG_MONGER_PULL;
+  const uint32_t direct_flags = GOSSIP_FLAG_DIRECT | GOSSIP_FLAG_TOPO_PEERS | GOSSIP_FLAG_MONGER | GOSSIP_FLAG_MONGER_PULL |
+                                GOSSIP_FLAG_MONGER_PUSHPULL;
   e->fw.D = cfg->stall_rounds;
 
   auto bail = [&](int rc) {
@@ -1600,9 +1631,10 @@ int gossip_create(const gossip_config_t* cfg, gossip_engine_t** out) {
     return bail(GOSSIP_ENOMEM);
   }
   if (e->mongering() && (!alloc(e->hot, shard / 8) || !alloc(e->hot_next, shard / 8))) return bail(GOSSIP_ENOMEM);
-  if (e->monger_pull && (!alloc(e->mp_need, shard / 8) || !alloc(e->mp_less, shard / 8) ||
-                         (e->W > 1 && !alloc(e->mp_map, (e->N + 63) / 64))))
+  if (e->hot_stop() && (!alloc(e->mp_need, shard / 8) || !alloc(e->mp_less, shard / 8) ||
+                        (e->W > 1 && !alloc(e->mp_map, (e->N + 63) / 64))))
     return bail(GOSSIP_ENOMEM);
+  if (e->monger_pushpull && !alloc(e->pp_gain, shard / 8)) return bail(GOSSIP_ENOMEM);
   bind_slices(e);
   if (e->mode != GOSSIP_MODE_FLOOD && e->mode != GOSSIP_MODE_ANTIENTROPY && !(cfg->flags & direct_flags) &&
       bin_path_ok(e->N, e->k, e->W, G)) {
@@ -2054,7 +2086,7 @@ int gossip_round_compute(gossip_engine_t* e, uint64_t* partial) {
   }
   if (int rc = timer_collect(e)) return rc;
   std::memcpy(partial, e->partial_h, part_len(e) * 8);
-  if (e->monger_pull) {  // the close pass's count of hot nodes rode in the internal slot
+  if (e->hot_stop()) {  // the close pass's count of hot nodes rode in the internal slot
     e->mp_hot_nodes = partial[4 + e->R];
     partial[4 + e->R] = 0;
   }
@@ -2667,7 +2699,7 @@ int gossip_ae_finish(gossip_engine_t* e, uint64_t* partial) {
 int gossip_set_monger(gossip_engine_t* e, uint32_t cool, uint32_t blind) {
   if (!e) return GOSSIP_EINVAL;
   if (!e->mongering())
-    return e->fail(GOSSIP_ESTATE, "gossip_set_monger needs an engine created with GOSSIP_FLAG_MONGER or _MONGER_PULL");
+    return e->fail(GOSSIP_ESTATE, "gossip_set_monger needs an engine created with GOSSIP_FLAG_MONGER, _MONGER_PULL or _MONGER_PUSHPULL");
   if (blind > 1) return e->fail(GOSSIP_EINVAL, "blind must be 0 or 1");
   e->cool = cool;
   e->blind = blind;
@@ -2677,7 +2709,7 @@ int gossip_set_monger(gossip_engine_t* e, uint32_t cool, uint32_t blind) {
 int gossip_set_monger_limit(gossip_engine_t* e, uint32_t limit) {
   if (!e) return GOSSIP_EINVAL;
   if (!e->mongering())
-    return e->fail(GOSSIP_ESTATE, "gossip_set_monger_limit needs an engine created with GOSSIP_FLAG_MONGER or _MONGER_PULL");
+    return e->fail(GOSSIP_ESTATE, "gossip_set_monger_limit needs an engine created with GOSSIP_FLAG_MONGER, _MONGER_PULL or _MONGER_PUSHPULL");
   if (limit < 1 || limit > 15) return e->fail(GOSSIP_EINVAL, "limit must be in [1, 15]");
   if (limit > 1 && !e->counts) {  // counts are kept from here on: what cooled before reads 0
     if (int rc = set_dev(e)) return rc;
@@ -2779,7 +2811,8 @@ int gossip_step(gossip_engine_t* e, uint32_t max_rounds, gossip_round_stats_t* s
     // pull mongering: until the first round that leaves no node hot (reported).  Not
     // at messages == 0: a round in which nobody happens to pull from a hot node sends nothing while
     // rumors are still hot
-    if (e->monger_pull) {
+    // push-pull mongering (§2.16) ends the same way
+    if (e->hot_stop()) {
       if (e->mp_hot_nodes == 0) break;
       continue;
     }
@@ -2815,7 +2848,7 @@ int gossip_read_shard(gossip_engine_t* e, uint64_t* out, uint64_t n_words) {
 int gossip_read_hot_shard(gossip_engine_t* e, uint64_t* out, uint64_t n_words) {
   if (!e || !out) return GOSSIP_EINVAL;
   if (!e->mongering())
-    return e->fail(GOSSIP_ESTATE, "gossip_read_hot_shard needs an engine created with GOSSIP_FLAG_MONGER or _MONGER_PULL");
+    return e->fail(GOSSIP_ESTATE, "gossip_read_hot_shard needs an engine created with GOSSIP_FLAG_MONGER, _MONGER_PULL or _MONGER_PUSHPULL");
   if (n_words < (uint64_t)e->W * e->nown) return e->fail(GOSSIP_EINVAL, "output too small");
   if (int rc = set_dev(e)) return rc;
   HIP_OK(e, hipStreamSynchronize(e->stream));
@@ -2827,7 +2860,7 @@ int gossip_read_hot_shard(gossip_engine_t* e, uint64_t* out, uint64_t n_words) {
 int gossip_read_monger_counts(gossip_engine_t* e, uint64_t* out, uint64_t n_words) {
   if (!e || !out) return GOSSIP_EINVAL;
   if (!e->mongering())
-    return e->fail(GOSSIP_ESTATE, "gossip_read_monger_counts needs an engine created with GOSSIP_FLAG_MONGER or _MONGER_PULL");
+    return e->fail(GOSSIP_ESTATE, "gossip_read_monger_counts needs an engine created with GOSSIP_FLAG_MONGER, _MONGER_PULL or _MONGER_PUSHPULL");
   const uint64_t plane = (uint64_t)e->W * e->nown;
   if (n_words != 4 * plane) return e->fail(GOSSIP_EINVAL, "n_words must be 4 * W * Nl_owned");
   if (!e->counts) {  // no limit above 1 yet: nothing was counted
@@ -2846,7 +2879,7 @@ int gossip_read_monger_counts(gossip_engine_t* e, uint64_t* out, uint64_t n_word
 int gossip_monger_hot_nodes(gossip_engine_t* e, uint64_t* out) {
   if (!e || !out) return GOSSIP_EINVAL;
   if (!e->mongering())
-    return e->fail(GOSSIP_ESTATE, "gossip_monger_hot_nodes needs an engine created with GOSSIP_FLAG_MONGER or _MONGER_PULL");
+    return e->fail(GOSSIP_ESTATE, "gossip_monger_hot_nodes needs an engine created with GOSSIP_FLAG_MONGER, _MONGER_PULL or _MONGER_PUSHPULL");
   if (int rc = set_dev(e)) return rc;
   HIP_OK(e, hipMemsetAsync(e->scratch_d, 0, 8, e->stream));
   HIP_OK(e, launch_monger_hot_scan(e->hot, e->N, e->W, nullptr, e->scratch_d, e->stream));

@@ -21,7 +21,7 @@
 // blind is a run-time value, as in monger.hip: both variants gather H_t[p].
 #include "monger_pull.h"
 
-#include "planes.h"
+#include "monger_close.h"
 #include "sender.h"
 
 namespace gossip {
@@ -151,25 +151,7 @@ __global__ __launch_bounds__(kSenderBlock) void monger_pull_close_kernel(MongerP
         if (nd | ls) {
           if (nd) m.need[at] = 0;
           if (ls) m.less[at] = 0;
-          if (coin < 0) coin = m.cool && cool_draws((uint32_t)s, a.t, 0u, a.key0, a.key1).x < m.cool;
-          const uint64_t inc = coin ? ls & ~nd : 0ull;
-          uint64_t clear = inc;
-          if (COUNT) {
-            uint64_t c[4];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) c[b] = m.C[(uint64_t)b * plane + at];
-            const uint64_t reset = nd & (c[0] | c[1] | c[2] | c[3]);
-#pragma unroll
-            for (int b = 0; b < 4; ++b) c[b] &= ~nd;
-            if (inc) {
-              planes_add(c, inc);
-              clear = planes_ge(c, m.limit) & inc;
-            }
-            if (reset | inc) {
-#pragma unroll
-              for (int b = 0; b < 4; ++b) m.C[(uint64_t)b * plane + at] = c[b];
-            }
-          }
+          const uint64_t clear = monger_cool_word<COUNT>(m, s, at, plane, nd, ls, coin);  // (monger_close.h)
           if (clear) {
             hn &= ~clear;
             m.Hnext[at] = hn;

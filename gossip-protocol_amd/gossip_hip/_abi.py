@@ -20,6 +20,7 @@ FLAG_TOPO_PEERS = 1 << 6  # random modes: peers drawn from the node's topology r
 FLAG_AE_TOPO_PEERS = 1 << 7  # ANTIENTROPY: exchange peers drawn from the node's topology row
 FLAG_MONGER = 1 << 8  # PUSH: rumor mongering, nodes lose interest in what they push
 FLAG_MONGER_PULL = 1 << 9  # PULL: hot nodes answer pulls and cool by the pullers' feedback
+FLAG_MONGER_PUSHPULL = 1 << 10  # PUSHPULL: both ends of an exchange send their hot rumors and cool by feedback
 
 ABI_VERSION = 10  # include/gossip.h GOSSIP_ABI_VERSION (v10: gossip_round_wall)
 

@@ -472,12 +472,14 @@ class Engine(AbiEngine):
         contact makes the sender lose interest, a probability (float, turned into x / 2^32 by
         loss_threshold) or the u32 threshold itself (int); blind: every attempt counts, else feedback.
         FLAG_MONGER_PULL (§2.15): the chance that a round's needless pulls count at the server; blind:
-        every delivered request counts every hot rumor as needless."""
+        every delivered request counts every hot rumor as needless.  FLAG_MONGER_PUSHPULL (§2.16): the
+        same at both ends of every delivered exchange."""
         x = loss_threshold(cool) if isinstance(cool, float) else int(cool)
         self._check(self._fn("set_monger")(self._h, C.c_uint32(x), C.c_uint32(int(blind))))
 
     def read_hot(self) -> np.ndarray:
-        """FLAG_MONGER: the rumors each node is still spreading, shaped like read_shard()."""
+        """FLAG_MONGER, FLAG_MONGER_PULL and FLAG_MONGER_PUSHPULL: the rumors each node is still spreading,
+        shaped like read_shard()."""
         n = self.hi - self.lo
         out = np.zeros(self.n_words * n, dtype=np.uint64)
         self._check(self._fn("read_hot_shard")(self._h, out.ctypes.data_as(_abi.U64P), C.c_uint64(out.size)))
@@ -486,11 +488,13 @@ class Engine(AbiEngine):
     def set_monger_limit(self, limit: int):
         """FLAG_MONGER with counters, for the rounds that follow: a rumor cools only
         once `limit` (1..15) of its counted contacts have passed set_monger's coin; 1, the value after
-        create, is the coin alone.  Counts are kept from the first limit above 1 on."""
+        create, is the coin alone.  Counts are kept from the first limit above 1 on.  FLAG_MONGER_PULL
+        and FLAG_MONGER_PUSHPULL (§2.15, §2.16): a round adds at most one to a count, and a contact that
+        needed the rumor sets it back to 0."""
         self._check(self._fn("set_monger_limit")(self._h, C.c_uint32(int(limit))))
 
     def read_counts(self) -> np.ndarray:
-        """FLAG_MONGER: the count of every owned node and rumor, uint8 [n_rumors, n] (zeros while no
+        """Any mongering flag: the count of every owned node and rumor, uint8 [n_rumors, n] (zeros while no
         limit above 1 was set), unpacked from gossip_read_monger_counts' four bit planes."""
         n = self.hi - self.lo
         planes = np.zeros(4 * self.n_words * n, dtype=np.uint64)
@@ -503,8 +507,9 @@ class Engine(AbiEngine):
         return out
 
     def hot_nodes(self) -> int:
-        """FLAG_MONGER and FLAG_MONGER_PULL: the nodes that hold a hot rumor in the current state (a
-        FLAG_MONGER_PULL step ends with the first round that leaves none)."""
+        """FLAG_MONGER, FLAG_MONGER_PULL and FLAG_MONGER_PUSHPULL: the nodes that hold a hot rumor in the
+        current state (a FLAG_MONGER_PULL or FLAG_MONGER_PUSHPULL step ends with the first round that
+        leaves none)."""
         out = C.c_uint64()
         self._check(self._fn("monger_hot_nodes")(self._h, C.byref(out)))
         return out.value

@@ -16,7 +16,11 @@
 //                               (GOSSIP_FLAG_MONGER_PULL), the node that answered cools with
 //                               probability P once per round in which a pull did not need the rumor
 //                               and none did (--blind: every pull that arrives counts); runs until
-//                               no node is hot; the messages are the replies that carried a rumor
+//                               no node is hot; the messages are the replies that carried a rumor.
+//                               With pushpull, or pushpull-grid --topo-peers: push-pull rumor mongering
+//                               (GOSSIP_FLAG_MONGER_PUSHPULL), both ends of an exchange send their hot
+//                               rumors and both cool as the answering node of pull does; runs until no
+//                               node is hot; the messages are the exchanges with a hot end
 //              [--monger-limit M]   with --monger: the counter rule (gossip_set_monger_limit), a
 //                               rumor cools once M (1..15) counted contacts have passed the coin;
 //                               the paper's pure counter is --monger 1 --monger-limit M
@@ -100,12 +104,13 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--topo-peers goes with push-grid, pull-grid or pushpull-grid (and they with it)\n");
     return 2;
   }
-  const bool monger_pull = monger >= 0 && base == "pull";
+  const bool monger_pull = monger >= 0 && base == "pull", monger_pp = monger >= 0 && base == "pushpull";
+  const bool by_hot = monger_pull || monger_pp;  // quiescence is judged by the hot nodes
   cfg.flags = (hash ? GOSSIP_FLAG_HASH : 0) | (topo_peers ? GOSSIP_FLAG_TOPO_PEERS : 0) |
-              (monger < 0 ? 0 : monger_pull ? GOSSIP_FLAG_MONGER_PULL : GOSSIP_FLAG_MONGER);
-  if ((monger >= 0 && ((base != "push" && base != "pull") || shards > 1 || monger > 1.0)) || (blind && monger < 0)) {
-    std::fprintf(stderr, "--monger P (0 <= P <= 1) goes with --mode push or pull, or push-grid or pull-grid "
-                         "--topo-peers, on one shard, --blind with --monger\n");
+              (monger < 0 ? 0 : monger_pp ? GOSSIP_FLAG_MONGER_PUSHPULL : monger_pull ? GOSSIP_FLAG_MONGER_PULL : GOSSIP_FLAG_MONGER);
+  if ((monger >= 0 && (base == "flood" || shards > 1 || monger > 1.0)) || (blind && monger < 0)) {
+    std::fprintf(stderr, "--monger P (0 <= P <= 1) goes with --mode push, pull or pushpull, or push-grid, pull-grid or "
+                         "pushpull-grid --topo-peers, on one shard, --blind with --monger\n");
     return 2;
   }
   if (limit_given && (monger < 0 || monger_limit < 1 || monger_limit > 15)) {
@@ -190,9 +195,9 @@ int main(int argc, char** argv) {
     const gossip_round_stats_t& last = st[done ? done - 1 : 0];
     uint64_t messages = 0;  // FLOOD and --topo-peers count them (0 for random gossip over all nodes)
     for (uint32_t r = 0; r < done; ++r) messages += st[r].messages;
-    if (monger >= 0) {  // rounds to quiescence, who never heard each rumor, what it cost (DESIGN.md §2.13, §2.15)
+    if (monger >= 0) {  // rounds to quiescence, who never heard each rumor, what it cost (DESIGN.md §2.13, §2.15, §2.16)
       uint64_t worst = 0, sum = 0, hot = 0;
-      if (monger_pull)  // quiescent: no node is hot (a round may send nothing while rumors are hot)
+      if (by_hot)  // quiescent: no node is hot (a round may send nothing while rumors are hot)
         if (int rc = gossip_monger_hot_nodes(e, &hot)) return die(e, "gossip_monger_hot_nodes", rc);
       for (uint32_t r = 0; done && r < rumors; ++r) {
         const uint64_t miss = nodes - infected[(size_t)(done - 1) * rumors + r];
@@ -204,7 +209,7 @@ int main(int argc, char** argv) {
                   "\"rounds\":%u,\"quiescent\":%u,\"converged\":%u,\"residue_max\":%llu,\"residue_mean\":%.3f,"
                   "\"messages\":%llu,\"messages_per_node\":%.4f,\"seconds\":%.6f,\"state_hash\":\"0x%016llx\"}\n",
                   run, mode.c_str(), monger, blind ? 1u : 0u, monger_limit, (unsigned long long)nodes, rumors, done,
-                  done && (monger_pull ? hot == 0 : last.messages == 0) ? 1u : 0u, last.converged, (unsigned long long)worst,
+                  done && (by_hot ? hot == 0 : last.messages == 0) ? 1u : 0u, last.converged, (unsigned long long)worst,
                   (double)sum / rumors, (unsigned long long)messages, (double)messages / (double)nodes, s,
                   (unsigned long long)last.state_hash);
       continue;

@@ -82,6 +82,11 @@ const (
 	// told it (SetMonger, SetMongerLimit); Step runs until a round leaves no node hot (HotNodes),
 	// and RoundStats.Messages counts the replies that carried a rumor.
 	FlagMongerPull Flags = Flags(C.GOSSIP_FLAG_MONGER_PULL)
+	// FlagMongerPushPull: PushPull as rumor mongering (DESIGN.md §2.16): every node starts k
+	// exchanges, both ends send the rumors they are still hot on, and both lose interest by what
+	// the round's exchanges told them (SetMonger, SetMongerLimit); Step runs until a round leaves no
+	// node hot (HotNodes), and RoundStats.Messages counts the exchanges in which an end was hot.
+	FlagMongerPushPull Flags = Flags(C.GOSSIP_FLAG_MONGER_PUSHPULL)
 )
 
 // Config mirrors gossip_config_t.  Probabilities are thresholds x / 2^32 (Threshold).
@@ -531,7 +536,7 @@ func (e *Engine) ReadMongerCounts() ([]uint64, error) {
 }
 
 // HotNodes returns the number of nodes that hold a hot rumor in the current state (FlagMonger,
-// FlagMongerPull).
+// FlagMongerPull, FlagMongerPushPull).
 func (e *Engine) HotNodes() (uint64, error) {
 	e.mu.Lock()
 	defer e.mu.Unlock()

@@ -114,7 +114,7 @@ enum gossip_flags {
                                           gossip_set_monger_limit adds the counter rule:
                                           a rumor cools only once `limit` of its counted contacts have
                                           passed the coin; the counts are read by gossip_read_monger_counts */
-  GOSSIP_FLAG_MONGER_PULL = 1u << 9    /* PULL: pull rumor mongering.  The engine keeps the
+  GOSSIP_FLAG_MONGER_PULL = 1u << 9,   /* PULL: pull rumor mongering.  The engine keeps the
                                           known and the hot rumors as a GOSSIP_FLAG_MONGER engine does.  Every
                                           node (with GOSSIP_FLAG_TOPO_PEERS: every node with a row) sends k
                                           pull requests per round to the peers an unflagged PULL engine of
@@ -137,6 +137,33 @@ enum gossip_flags {
                                           partitions; _DIRECT and _DENSE change nothing.  With any mode but
                                           PULL, or together with GOSSIP_FLAG_MONGER, gossip_create returns
                                           GOSSIP_EINVAL, with stall_rounds or shard_count > 1 GOSSIP_ENOTSUP */
+  GOSSIP_FLAG_MONGER_PUSHPULL = 1u << 10 /* PUSHPULL: push-pull rumor mongering.  The engine
+                                          keeps the known and the hot rumors, the counts and the knobs as a
+                                          GOSSIP_FLAG_MONGER_PULL engine does.  Every node (with
+                                          GOSSIP_FLAG_TOPO_PEERS: every node with a row) starts k exchanges
+                                          per round with the peers an unflagged PUSHPULL engine of the same
+                                          seed draws, a full or cold node too; an exchange lost by edge_loss
+                                          or partitions moves nothing and tells neither end anything.  In a
+                                          delivered exchange both ends send their hot rumors, hot at the
+                                          other end where they are new.  Both ends lose interest, each once
+                                          per round and rumor from all the exchanges it took part in, as
+                                          initiator or as target: a rumor some partner lacked has its count
+                                          set back to 0 and stays; else, if some partner held it and the
+                                          node's coin (one per node and round, Philox stream tag 5) is below
+                                          cool, its count goes up by one and it cools at `limit`
+                                          (gossip_set_monger, gossip_set_monger_limit; blind = 1: every
+                                          delivered exchange counts every hot rumor as held).
+                                          stats.messages counts the delivered exchanges in which at least
+                                          one end had something hot, once per exchange.  gossip_step runs
+                                          until the first round that leaves no node hot (reported), not
+                                          until converged and not until a round sends nothing.  With
+                                          cool = 0 (the value after create) the engine equals an unflagged
+                                          PUSHPULL engine bit for bit.  Composes with GOSSIP_FLAG_TOPO_PEERS,
+                                          _HASH and _TIMING and with edge_loss / partitions; _DIRECT and
+                                          _DENSE change nothing.  With any mode but PUSHPULL, or together
+                                          with GOSSIP_FLAG_MONGER or GOSSIP_FLAG_MONGER_PULL, gossip_create
+                                          returns GOSSIP_EINVAL, with stall_rounds or shard_count > 1
+                                          GOSSIP_ENOTSUP */
 };
 
 typedef struct gossip_config {
@@ -196,6 +223,9 @@ typedef struct gossip_round_stats {
                            GOSSIP_FLAG_MONGER_PULL: the delivered pull requests whose server had
                            something hot, the replies that carried a rumor; an exchange with oneself
                            over a self-loop included;
+                           GOSSIP_FLAG_MONGER_PUSHPULL: the delivered exchanges in which at least
+                           one end had something hot, once per exchange; an exchange of a hot
+                           node with itself over a self-loop included;
                            other random-mode engines: 0                              */
   uint64_t state_hash;  /* GOSSIP_FLAG_HASH: Σ mix64 over nonzero words, else 0   */
 } gossip_round_stats_t;
@@ -289,13 +319,13 @@ int gossip_set_param(gossip_engine_t* eng, const char* name, double value);
 int gossip_set_topology_csr(gossip_engine_t* eng, const uint32_t* row_ptr, const uint32_t* col,
                             uint64_t n, uint64_t n_edges);
 
-/* Clears every rumor bit (GOSSIP_FLAG_MONGER and _MONGER_PULL: the hot bits and the counts too; cool, blind and the
+/* Clears every rumor bit (GOSSIP_FLAG_MONGER, _MONGER_PULL and _MONGER_PUSHPULL: the hot bits and the counts too; cool, blind and the
  * limit stay) and sets t = 0. */
 int gossip_reset(gossip_engine_t* eng);
 
 /* Client broadcast of rumor slot `rumor` to `node` (no-op when the node is
  * outside this shard or already holds it — the dedupe of main.go:113).
- * GOSSIP_FLAG_MONGER and _MONGER_PULL: the rumor is hot at a node it is new at; one the node holds
+ * GOSSIP_FLAG_MONGER, _MONGER_PULL and _MONGER_PUSHPULL: the rumor is hot at a node it is new at; one the node holds
  * already, cooled or not, stays as it is, and so does its count (gossip_inject_random likewise).
  * ANTIENTROPY: a local write of key `rumor` at `node` (its version + 1). */
 int gossip_inject(gossip_engine_t* eng, uint64_t node, uint32_t rumor);
@@ -317,7 +347,9 @@ int gossip_set_faults(gossip_engine_t* eng, uint32_t edge_loss, uint32_t partiti
  * delivered or lost.  After create cool = 0 and blind = 0; gossip_reset keeps both.  GOSSIP_ESTATE on
  * an engine created without the flag, GOSSIP_EINVAL for blind > 1.  A counted contact whose coin holds
  * cools at once while the limit is 1 (the value after create), else it is counted first:
- * gossip_set_monger_limit. */
+ * gossip_set_monger_limit.  GOSSIP_FLAG_MONGER_PULL (§2.15) and GOSSIP_FLAG_MONGER_PUSHPULL (§2.16) take the
+ * call too: cool = P(a round's needless contacts count at the node), one coin per node and round; blind = 1:
+ * every delivered request (push-pull: exchange, at both ends) counts every hot rumor as held. */
 int gossip_set_monger(gossip_engine_t* eng, uint32_t cool, uint32_t blind);
 
 /* GOSSIP_FLAG_MONGER with counters, for the rounds that follow: limit in 1..15.  Every
@@ -331,7 +363,8 @@ int gossip_set_monger(gossip_engine_t* eng, uint32_t cool, uint32_t blind);
  * coin holds, not before.  GOSSIP_ESTATE on an engine created without the flag, GOSSIP_EINVAL for 0 or
  * more than 15, GOSSIP_ENOMEM when the counts cannot be allocated (engine and limit then unchanged).
  * GOSSIP_FLAG_MONGER_PULL takes both calls too: there the counts are the server's, a round
- * adds at most one to a count, and a pull that needed the rumor sets it back to 0. */
+ * adds at most one to a count, and a pull that needed the rumor sets it back to 0.
+ * GOSSIP_FLAG_MONGER_PUSHPULL likewise: the counts are those of both ends of an exchange. */
 int gossip_set_monger_limit(gossip_engine_t* eng, uint32_t limit);
 
 /* Runs rounds until converged (FLOOD also: a round that sends nothing) or max_rounds
@@ -339,7 +372,7 @@ int gossip_set_monger_limit(gossip_engine_t* eng, uint32_t limit);
  * reported) or max_rounds, and not until converged; on return gossip_round_index and the state
  * are those of the last reported round.  GOSSIP_FLAG_MONGER_PULL: until the first round that leaves no
  * node hot (reported; gossip_monger_hot_nodes is then 0) or max_rounds — a round that sends nothing
- * while rumors are hot does not end the run.  stats: max_rounds entries or NULL; infected: max_rounds * R
+ * while rumors are hot does not end the run; GOSSIP_FLAG_MONGER_PUSHPULL: the same rule.  stats: max_rounds entries or NULL; infected: max_rounds * R
  * counters (row t = per-rumor infected counts after round t) or NULL.
  * G > 1: the engine needs its collectives first (gossip_comm_init_rank below); every
  * rank calls gossip_step with the same max_rounds and gets the same global stats. */
@@ -384,20 +417,20 @@ const char* gossip_group_last_error(const gossip_group_t* grp);
  * or the whole owned shard in logical order out[w * Nl_owned + i]. */
 int gossip_read_bitset(gossip_engine_t* eng, uint64_t node, uint64_t* out, uint32_t nwords);
 int gossip_read_shard(gossip_engine_t* eng, uint64_t* out, uint64_t n_words);
-/* GOSSIP_FLAG_MONGER: the rumors every node is still hot on, in the layout of gossip_read_shard (a
- * subset of it); GOSSIP_ESTATE on an engine created without the flag. */
+/* GOSSIP_FLAG_MONGER, _MONGER_PULL and _MONGER_PUSHPULL: the rumors every node is still hot on, in the
+ * layout of gossip_read_shard (a subset of it); GOSSIP_ESTATE on an engine created with none of the three. */
 int gossip_read_hot_shard(gossip_engine_t* eng, uint64_t* out, uint64_t n_words);
-/* GOSSIP_FLAG_MONGER: the counts of gossip_set_monger_limit as four bit planes in the layout of
+/* GOSSIP_FLAG_MONGER, _MONGER_PULL and _MONGER_PUSHPULL: the counts of gossip_set_monger_limit as four bit planes in the layout of
  * gossip_read_shard, bit b of the count of rumor 64 w + j at node lo + i = bit j of
  * out[(b * W + w) * Nl_owned + i]; n_words must be 4 * W * Nl_owned (else GOSSIP_EINVAL).  All zero
  * while no limit above 1 was ever set.  GOSSIP_ESTATE on an engine created without the flag. */
 int gossip_read_monger_counts(gossip_engine_t* eng, uint64_t* out, uint64_t n_words);
-/* GOSSIP_FLAG_MONGER and _MONGER_PULL: the number of nodes that hold a hot rumor in the current state
- * (after gossip_step on a GOSSIP_FLAG_MONGER_PULL engine: 0 unless max_rounds ended the run).
- * gossip_read_hot_shard and gossip_read_monger_counts work on both flags alike.  A host that runs
- * the gossip_round_* calls itself instead of gossip_step applies GOSSIP_FLAG_MONGER_PULL's stop rule
- * with this call: the partial vector does not carry the number.  GOSSIP_ESTATE on an engine created
- * with neither flag, GOSSIP_EINVAL for a null argument. */
+/* GOSSIP_FLAG_MONGER, _MONGER_PULL and _MONGER_PUSHPULL: the number of nodes that hold a hot rumor in the
+ * current state (after gossip_step on a GOSSIP_FLAG_MONGER_PULL or _MONGER_PUSHPULL engine: 0 unless
+ * max_rounds ended the run).  gossip_read_hot_shard and gossip_read_monger_counts work on all three
+ * flags alike.  A host that runs the gossip_round_* calls itself instead of gossip_step applies the stop
+ * rule of GOSSIP_FLAG_MONGER_PULL and _MONGER_PUSHPULL with this call: the partial vector does not carry the
+ * number.  GOSSIP_ESTATE on an engine created with none of the flags, GOSSIP_EINVAL for a null argument. */
 int gossip_monger_hot_nodes(gossip_engine_t* eng, uint64_t* out);
 /* ANTIENTROPY readout: the K versions of one node (owned by this shard), and its alive flag. */
 int gossip_read_versions(gossip_engine_t* eng, uint64_t node, uint32_t* out, uint32_t ncomp, uint32_t* alive);

@@ -1,4 +1,4 @@
-"""Rumor mongering at scale (DESIGN.md §3.11, §3.12, §3.13): one engine of 2^log2 nodes, R = 64, k = 2,
+"""Rumor mongering at scale (DESIGN.md §3.11, §3.12, §3.13, §3.14): one engine of 2^log2 nodes, R = 64, k = 2,
 uniform peers, inject_random, run to quiescence one round per gossip_step with GOSSIP_FLAG_TIMING;
 after each round timer 0 (the seed copies and the round kernel) and timer 1 (the stats pass) are
 read.  One untimed run, then `runs` timed ones.  Prints one JSON line: rounds, the residue per
@@ -9,8 +9,10 @@ the call can run); --planes sets the limit to 2 and back to 1 first, so that the
 through the counter kernel (§2.14 item 9); --pkg names another build's package directory to
 measure that one instead.  --pull runs a PULL engine with GOSSIP_FLAG_MONGER_PULL (§2.15, §3.13): timer 0
 is then the request and the close pass, a run ends with the first round that leaves no node hot, and
-the messages are the replies that carried a rumor.
-Usage: monger_probe.py [--log2 24] [--cool 0.5|always] [--limit 0] [--planes] [--blind] [--pull] [--runs 3]
+the messages are the replies that carried a rumor.  --pushpull runs a PUSHPULL engine with
+GOSSIP_FLAG_MONGER_PUSHPULL (§2.16, §3.14): the same timers and stop rule, and the messages are the exchanges
+in which an end was hot.
+Usage: monger_probe.py [--log2 24] [--cool 0.5|always] [--limit 0] [--planes] [--blind] [--pull | --pushpull] [--runs 3]
                        [--pkg DIR [--build NAME]]"""
 import argparse
 import json
@@ -24,6 +26,7 @@ ap.add_argument("--limit", type=int, default=0)
 ap.add_argument("--blind", action="store_true")
 ap.add_argument("--planes", action="store_true")
 ap.add_argument("--pull", action="store_true")
+ap.add_argument("--pushpull", action="store_true")
 ap.add_argument("--runs", type=int, default=3)
 ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED0003)
 ap.add_argument("--build", default="this tree", help="a name for the measured build, echoed in the JSON line")
@@ -35,6 +38,10 @@ from gossip_hip import FLAG_MONGER, FLAG_TIMING, Engine  # noqa: E402
 
 if a.pull:
     from gossip_hip import FLAG_MONGER_PULL  # noqa: E402  (not in a build from before the flag)
+if a.pushpull:
+    from gossip_hip import FLAG_MONGER_PUSHPULL  # noqa: E402  (likewise)
+assert not (a.pull and a.pushpull)
+by_hot = a.pull or a.pushpull   # the run ends when no node is hot
 
 N, R, K, CAP = 1 << a.log2, 64, 2, 1024
 cool = 2 ** 32 - 1 if a.cool == "always" else float(a.cool)
@@ -45,8 +52,8 @@ def rng(xs):
 
 
 runs = []
-with Engine(N, R, "pull" if a.pull else "push", K, a.seed,
-            flags=(FLAG_MONGER_PULL if a.pull else FLAG_MONGER) | FLAG_TIMING) as e:
+with Engine(N, R, "pushpull" if a.pushpull else "pull" if a.pull else "push", K, a.seed,
+            flags=(FLAG_MONGER_PUSHPULL if a.pushpull else FLAG_MONGER_PULL if a.pull else FLAG_MONGER) | FLAG_TIMING) as e:
     e.set_monger(cool, a.blind)
     if a.planes:
         e.set_monger_limit(2)
@@ -62,7 +69,7 @@ with Engine(N, R, "pull" if a.pull else "push", K, a.seed,
             res = e.step(1)
             t0, t1 = e.kernel_time(0)[0] * 1e3, e.kernel_time(1)[0] * 1e3
             per_round.append((res.stats[0]["messages"], t0, t1, res.stats[0]["full_nodes"], res.infected[0]))
-            if (e.hot_nodes() if a.pull else res.stats[0]["messages"]) == 0:
+            if (e.hot_nodes() if by_hot else res.stats[0]["messages"]) == 0:
                 break
         if rep:
             runs.append(per_round)
@@ -81,7 +88,7 @@ def us(idx, col):
 
 
 print(json.dumps({
-    "build": a.build, "pull": a.pull, "nodes": N, "rumors": R, "fanout": K, "cool": a.cool, "blind": a.blind, "limit": a.limit, "planes": a.planes,
+    "build": a.build, "pull": a.pull, "pushpull": a.pushpull, "nodes": N, "rumors": R, "fanout": K, "cool": a.cool, "blind": a.blind, "limit": a.limit, "planes": a.planes,
     "rounds": len(last), "residue_nodes": [min(miss), max(miss)], "residue_share": [min(miss) / N, max(miss) / N],
     "full_nodes": last[-1][3], "messages_per_node": sum(p[0] for p in last) / N,
     "peak_round": peak, "peak_messages": last[peak][0],

@@ -1,6 +1,6 @@
-"""Rumor mongering's residue against its traffic, the three tables of
-Demers et al., "Epidemic algorithms for replicated database maintenance", on the GPU engine: one rumor
-injected at node 0 of N nodes, uniform peers, one run to quiescence per row.
+"""Rumor mongering's residue against its traffic, the three tables
+of Demers et al., "Epidemic algorithms for replicated database maintenance", and a fourth for push-pull,
+on the GPU engine: one rumor injected at node 0 of N nodes, uniform peers, one run to quiescence per row.
 
   feedback + counter   cool = 2^32 - 1 (a coin that fails with probability 2^-32), limit = m:
                        a sender loses interest after m pushes to peers that knew the rumor
@@ -9,6 +9,10 @@ injected at node 0 of N nodes, uniform peers, one run to quiescence per row.
   pull, feedback +     GOSSIP_FLAG_MONGER_PULL, cool = 2^32 - 1, limit = m: a node that answers pulls
   counter              loses interest after m rounds in which a pull did not need the rumor and no pull
                        did; the messages are the replies that carried the rumor
+  push-pull, feedback  GOSSIP_FLAG_MONGER_PUSHPULL, cool = 2^32 - 1, limit = m: both ends of an exchange
+  + counter            send the rumor while hot, and each loses interest after m rounds in which a
+                       partner held the rumor and none lacked it; the messages are the exchanges in
+                       which an end was hot
 
 Per m it prints the residue (the share of nodes that never heard the rumor), the messages per node
 and the rounds to quiescence (the quiescent round included).  The paper's figures (N = 1000, its own
@@ -20,20 +24,23 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gossip-protocol_amd"))
-from gossip_hip import FLAG_MONGER, FLAG_MONGER_PULL, Engine  # noqa: E402
+from gossip_hip import FLAG_MONGER, FLAG_MONGER_PULL, FLAG_MONGER_PUSHPULL, Engine  # noqa: E402
 
 ALWAYS = 2 ** 32 - 1
 CAP = 4096
 
 
-def row(n, k, seed, cool, blind, limit, pull=False):
-    with Engine(n, 1, "pull" if pull else "push", k, seed, flags=FLAG_MONGER_PULL if pull else FLAG_MONGER) as e:
+KINDS = {"push": FLAG_MONGER, "pull": FLAG_MONGER_PULL, "pushpull": FLAG_MONGER_PUSHPULL}
+
+
+def row(n, k, seed, cool, blind, limit, mode="push"):
+    with Engine(n, 1, mode, k, seed, flags=KINDS[mode]) as e:
         e.set_monger(cool, blind)
         if limit > 1:
             e.set_monger_limit(limit)
         e.inject(0, 0)
         res = e.step(CAP)
-        quiet = e.hot_nodes() == 0 if pull else res.stats[-1]["messages"] == 0
+        quiet = e.hot_nodes() == 0 if mode != "push" else res.stats[-1]["messages"] == 0
     assert quiet, "not quiescent after %d rounds" % CAP
     heard = int(res.infected[-1][0])
     return (n - heard) / n, sum(s["messages"] for s in res.stats) / n, res.rounds
@@ -50,7 +57,9 @@ def main():
     print(f"N = 2^{a.log2}, k = {a.fanout}, one rumor at node 0, seed {a.seed:#x}")
     for title, args in (("feedback, counter (cool = 2^32 - 1, limit = m)", lambda m: (ALWAYS, False, m)),
                         ("blind, coin (cool = 1 / m, limit = 1)", lambda m: (1.0 / m, True, 1)),
-                        ("pull, feedback, counter (cool = 2^32 - 1, limit = m)", lambda m: (ALWAYS, False, m, True))):
+                        ("pull, feedback, counter (cool = 2^32 - 1, limit = m)", lambda m: (ALWAYS, False, m, "pull")),
+                        ("push-pull, feedback, counter (cool = 2^32 - 1, limit = m)",
+                         lambda m: (ALWAYS, False, m, "pushpull"))):
         print(f"\n{title}\n| m | residue | messages per node | rounds |\n|---|---|---|---|")
         for m in range(1, a.max_m + 1):
             s, msgs, rounds = row(n, a.fanout, a.seed, *args(m))

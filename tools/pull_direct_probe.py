@@ -3,7 +3,9 @@ monger_probe.py's setup (2^log2 nodes, R = 64, k = 2, uniform peers, inject_rand
 one gossip_step per round to converged, timer 0 (seed copy + round kernel) + timer 1 (stats) read after
 each.  One untimed run, then three timed ones.  Prints one JSON line: rounds, the range of every
 round's device time over the timed runs (round_us), the slowest round and the whole run.
-Usage: pull_direct_probe.py [--log2 24]"""
+--mode pushpull: the same for a PUSHPULL engine, the baseline column of §3.14; --pkg names another
+build's package directory to measure that one instead.
+Usage: pull_direct_probe.py [--log2 24] [--mode pull|pushpull] [--pkg DIR [--build NAME]]"""
 import argparse
 import json
 import os
@@ -11,13 +13,17 @@ import sys
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--log2", type=int, default=24)
+ap.add_argument("--mode", default="pull", choices=["pull", "pushpull"])
+ap.add_argument("--build", default="this tree", help="a name for the measured build, echoed in the JSON line")
+ap.add_argument("--pkg", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                              "gossip-protocol_amd"))
 a = ap.parse_args()
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gossip-protocol_amd"))
+sys.path.insert(0, a.pkg)
 from gossip_hip import FLAG_DIRECT, FLAG_TIMING, Engine  # noqa: E402
 
 N, R, K = 1 << a.log2, 64, 2
 runs = []
-with Engine(N, R, "pull", K, 0x5EED0003, flags=FLAG_DIRECT | FLAG_TIMING) as e:
+with Engine(N, R, a.mode, K, 0x5EED0003, flags=FLAG_DIRECT | FLAG_TIMING) as e:
     for rep in range(4):
         e.reset()
         e.inject_random()
@@ -33,7 +39,7 @@ with Engine(N, R, "pull", K, 0x5EED0003, flags=FLAG_DIRECT | FLAG_TIMING) as e:
 last = runs[-1]
 worst = max(range(len(last)), key=lambda i: last[i][0] + last[i][1])
 print(json.dumps({
-    "build": "this tree", "engine": "PULL, GOSSIP_FLAG_DIRECT", "nodes": N, "rumors": R, "fanout": K, "rounds": len(last),
+    "build": a.build, "engine": a.mode.upper() + ", GOSSIP_FLAG_DIRECT", "nodes": N, "rumors": R, "fanout": K, "rounds": len(last),
     "round_us": [[round(min(r[i][0] + r[i][1] for r in runs), 1), round(max(r[i][0] + r[i][1] for r in runs), 1)]
                  for i in range(len(last))],
     "slowest_round": worst,
