@@ -30,6 +30,7 @@
 #include <immintrin.h>
 #include "kernels.h"
 #include "monger.h"
+#include "monger_conn.h"
 #include "monger_pull.h"
 #include "monger_pushpull.h"
 #include "multi.h"
@@ -121,6 +122,12 @@ struct gossip_engine {
   // gains of one round [W][N] (all zero between rounds: no reset or inject touches them)
   bool monger_pushpull = false;
   DevBuf<uint64_t> pp_gain;
+  // connection limit and hunting, all three flags: c slots of keys per node [c][N],
+  // held from the first limit above 0 on (conn_cap: the limit they were allocated for), and the
+  // counters of the last round (conn_ran: that round ran under a limit; a reset clears it)
+  uint32_t conn_c = 0, conn_h = 0, conn_cap = 0;  // gossip_set_monger_connections
+  DevBuf<uint64_t> conn_slots, conn_cnt;
+  bool conn_ran = false;
   bool mongering() const { return monger || monger_pull || monger_pushpull; }
   bool hot_stop() const { return monger_pull || monger_pushpull; }  // the run ends when no node is hot
   // stall mode, random modes: streak per node, all N nodes on every shard
@@ -1242,10 +1249,19 @@ int compute_round(gossip_engine* e, const uint64_t* gathered) {
     }
     // timer 0 covers the whole S_t -> S_{t+1} transform (seed copy + round kernel)
     if ((rc = timer_begin(e, 0))) return rc;
+    ConnArgs conn{nullptr, nullptr, 0u, 0u};
+    e->conn_ran = e->mongering() && e->conn_c != 0;
+    if (e->conn_ran) {  // connection limit: the verdicts of the round's edges, before any request pass
+      conn = ConnArgs{e->conn_slots, e->conn_cnt, e->conn_c, e->conn_h};
+      HIP_OK(e, hipMemsetAsync(e->conn_slots, 0xFF, (size_t)e->conn_c * e->N * 8, e->stream));
+      HIP_OK(e, hipMemsetAsync(e->conn_cnt, 0, kConnCounters * 8, e->stream));
+      const ConnStageArgs cs{a, conn, e->monger ? (const uint64_t*)e->hot : nullptr, e->topo_peers};
+      HIP_OK(e, launch_conn_arbitrate(cs, e->stream));
+    }
     if (e->monger_pushpull) {  // push-pull mongering: request pass (ORs only), close pass (writes both next images whole)
       uint64_t* hot_nodes = e->partial_d + 4 + e->R;  // (the internal slot after infected[R], zeroed with the partials)
       const MongerPushPullArgs x{{a,       e->hot,  e->hot_next,   e->mp_need, e->mp_less, e->mp_map, hot_nodes,
-                                  e->cool, e->blind, e->topo_peers, e->counts,  e->limit},
+                                  e->cool, e->blind, e->topo_peers, e->counts,  e->limit,    conn},
                                  e->pp_gain};
       HIP_OK(e, launch_round_monger_pushpull(x, e->stream));
       HIP_OK(e, launch_monger_pushpull_close(x, e->stream));
@@ -1257,7 +1273,7 @@ int compute_round(gossip_engine* e, const uint64_t* gathered) {
     if (e->monger_pull) {  // pull mongering: request pass (writes both next images whole), close pass
       uint64_t* hot_nodes = e->partial_d + 4 + e->R;  // (the internal slot after infected[R], zeroed with the partials)
       const MongerPullArgs m{a,       e->hot,  e->hot_next,   e->mp_need, e->mp_less, e->mp_map, hot_nodes,
-                             e->cool, e->blind, e->topo_peers, e->counts,  e->limit};
+                             e->cool, e->blind, e->topo_peers, e->counts,  e->limit,    conn};
       HIP_OK(e, launch_round_monger_pull(m, e->stream));
       HIP_OK(e, launch_monger_pull_close(m, e->stream));
       if ((rc = timer_end(e, 0))) return rc;
@@ -1269,7 +1285,7 @@ int compute_round(gossip_engine* e, const uint64_t* gathered) {
     if (e->monger) {  // rumor mongering: H moves with S
       HIP_OK(e, hipMemcpyAsync(e->hot_next, e->hot, bytes, hipMemcpyDeviceToDevice, e->stream));
       // e->counts stays null until a limit above 1 is set: the counter forms (§2.14) run only from then on
-      const MongerArgs m{a, e->hot, e->hot_next, e->cool, e->blind, e->topo_peers, e->counts, e->limit};
+      const MongerArgs m{a, e->hot, e->hot_next, e->cool, e->blind, e->topo_peers, e->counts, e->limit, conn};
       HIP_OK(e, launch_round_monger(m, e->stream));
     } else if (e->topo_peers) {
       HIP_OK(e, launch_round_topo(a, e->stream));  // peers from the rows
@@ -1919,6 +1935,7 @@ int gossip_reset(gossip_engine_t* e) {
       if (e->mp_map) HIP_OK(e, hipMemsetAsync(e->mp_map, 0, (e->N + 63) / 64 * 8, e->stream));
       e->mp_map_ok = true;
       e->mp_hot_nodes = 0;
+      e->conn_ran = false;  // (the connection and hunt limits stay)
       HIP_OK(e, hipMemsetAsync(e->hot, 0, shard, e->stream));
       HIP_OK(e, hipMemsetAsync(e->hot_next, 0, shard, e->stream));
       if (e->counts) HIP_OK(e, hipMemsetAsync(e->counts, 0, 4 * shard, e->stream));  // (the limit stays)
@@ -2724,6 +2741,41 @@ int gossip_set_monger_limit(gossip_engine_t* e, uint32_t limit) {
   return GOSSIP_OK;
 }
 
+int gossip_set_monger_connections(gossip_engine_t* e, uint32_t conn_limit, uint32_t hunt_limit) {
+  if (!e) return GOSSIP_EINVAL;
+  if (!e->mongering())
+    return e->fail(GOSSIP_ESTATE, "gossip_set_monger_connections needs an engine created with GOSSIP_FLAG_MONGER, _MONGER_PULL or _MONGER_PUSHPULL");
+  if (conn_limit > kConnMaxLimit) return e->fail(GOSSIP_EINVAL, "conn_limit must be in [0, 8]");
+  if (hunt_limit > kConnMaxHunt) return e->fail(GOSSIP_EINVAL, "hunt_limit must be in [0, 15]");
+  if (conn_limit == 0 && hunt_limit != 0) return e->fail(GOSSIP_EINVAL, "hunt_limit needs a conn_limit above 0");
+  if (conn_limit > e->conn_cap) {  // the slots are kept from here on, also while the limit is 0
+    if (int rc = set_dev(e)) return rc;
+    const size_t n = (size_t)conn_limit * e->N;
+    DevBuf<uint64_t> slots, cnt;
+    if (slots.alloc(n, false) != hipSuccess || (!e->conn_cnt && cnt.alloc(kConnCounters, false) != hipSuccess))
+      return e->fail(GOSSIP_ENOMEM, "hipMalloc of %zu bytes for the connection slots failed", n * 8);
+    HIP_OK(e, hipStreamSynchronize(e->stream));  // a round in flight reads the slots that are replaced
+    e->conn_slots = std::move(slots);
+    if (!e->conn_cnt) e->conn_cnt = std::move(cnt);
+    e->conn_cap = conn_limit;
+  }
+  e->conn_c = conn_limit;
+  e->conn_h = hunt_limit;
+  return GOSSIP_OK;
+}
+
+int gossip_monger_connections(gossip_engine_t* e, uint64_t* out) {
+  if (!e || !out) return GOSSIP_EINVAL;
+  if (!e->mongering())
+    return e->fail(GOSSIP_ESTATE, "gossip_monger_connections needs an engine created with GOSSIP_FLAG_MONGER, _MONGER_PULL or _MONGER_PUSHPULL");
+  std::memset(out, 0, 4 * 8);
+  if (!e->conn_ran || e->conn_c == 0) return GOSSIP_OK;  // no round under a limit since create or reset, or no limit
+  if (int rc = set_dev(e)) return rc;
+  HIP_OK(e, hipStreamSynchronize(e->stream));
+  HIP_OK(e, hipMemcpy(out, e->conn_cnt, 4 * 8, hipMemcpyDeviceToHost));
+  return GOSSIP_OK;
+}
+
 int gossip_set_faults(gossip_engine_t* e, uint32_t edge_loss, uint32_t partitions) {
   if (!e) return GOSSIP_EINVAL;
   if ((edge_loss || partitions > 1) && e->mode == GOSSIP_MODE_FLOOD && !e->flood_edges)
@@ -2970,6 +3022,14 @@ uint32_t gossip_round_index(const gossip_engine_t* e) { return e ? e->t : 0; }
 uint32_t gossip_peer(uint64_t seed, uint64_t n_nodes, uint32_t node, uint32_t round, uint32_t j) {
   const u32x4 x = philox4x32_10(u32x4{node, round, 0u, j >> 2}, (uint32_t)seed, (uint32_t)(seed >> 32));
   return peer_from_word(lane_of(x, j & 3u), n_nodes - 1, node);
+}
+
+int gossip_monger_conn_words(uint64_t seed, uint32_t node, uint32_t round, uint32_t stage, uint32_t j, uint32_t* out) {
+  if (!out || stage > kConnMaxHunt || j > 63u) return GOSSIP_EINVAL;
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  out[0] = lane_of(conn_prio_draws(node, round, stage, j >> 2, k0, k1), j & 3u);
+  out[1] = lane_of(conn_hunt_draws(node, round, stage, j >> 2, k0, k1), j & 3u);
+  return GOSSIP_OK;
 }
 
 uint32_t gossip_topo_peer_index(uint64_t seed, uint32_t degree, uint32_t node, uint32_t round, uint32_t j) {

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "monger_conn.h"
 #include "philox.h"
 
 namespace gossip {
@@ -31,6 +32,9 @@ struct MongerArgs {
   // plane b of C[n][r] at C[(b * W + w) * N + n], r = 64 w + bit.  Only lane n reads or writes C[*][n].
   uint64_t* C;         // [4][W][N], updated in place; null: the engine holds no counters (the coin round)
   uint32_t limit;      // 1..15: a rumor cools at a counted contact that leaves its count at or above this
+  // Connection limit, after everything above for the same reason: conn.c == 0 is the
+  // unlimited round; else the slots hold the round's verdicts (launch_conn_arbitrate ran before)
+  ConnArgs conn;
 };
 
 // The cooling coins of edges 4q .. 4q + 3 of node n in round t: Philox stream tag 5.
@@ -39,7 +43,7 @@ __host__ __device__ __forceinline__ u32x4 cool_draws(uint32_t n, uint32_t t, uin
 }
 
 // One round: ORs the pushes into a.Snext and Hnext, clears the cooled bits of Hnext, and adds k per
-// initiating node to a.partial[2].  With m.C set, a coin that holds adds one to the count of every
+// initiating node to a.partial[2] (with m.conn.c set nothing: the arbitration counted the attempts).  With m.C set, a coin that holds adds one to the count of every
 // rumor of its counted set (saturating at 15), and a rumor cools when that leaves it at m.limit or more.
 hipError_t launch_round_monger(const MongerArgs& m, hipStream_t st);
 // Client broadcast: node >= 0 sets one bit, node < 0 every rumor at its tag-2 origin; the bit is

@@ -22,6 +22,10 @@
 // counts, and a rumor cools once its count reaches the limit.  Only an engine that holds counters
 // (gossip_set_monger_limit above 1) launches a COUNT form; no other engine pays for the planes by
 // a register, a load or a launch (§2.14 item 9).
+//
+// CONN: the engine holds a connection limit.  The arbitration of
+// monger_conn.hip has run; conn_resolve turns the stage-0 peers of a batch into the accepted targets,
+// and an edge that was refused for good is a lost one.  The unlimited forms keep their code.
 #include "monger.h"
 
 #include "planes.h"
@@ -102,7 +106,7 @@ __device__ __forceinline__ void close_word(const MongerArgs& m, uint64_t at, uin
 // The round.  Messages: k per node that initiates — something hot and,
 // over the topology, a row that is not empty — whether or not an attempt is lost.
 // ---------------------------------------------------------------------------
-template <bool ONE_WORD, bool TOPO, bool FAULTS, bool COUNT>
+template <bool ONE_WORD, bool TOPO, bool FAULTS, bool COUNT, bool CONN>
 __global__ __launch_bounds__(kSenderBlock) void round_monger_kernel(MongerArgs m) {
   const RoundArgs& a = m.a;
   uint64_t msgs = 0;
@@ -124,7 +128,7 @@ __global__ __launch_bounds__(kSenderBlock) void round_monger_kernel(MongerArgs m
       d = a.orow[n + 1] - b;
       if (d == 0) continue;
     }
-    msgs += a.k;
+    if (!CONN) msgs += a.k;  // (CONN: messages are the attempts, hunts included; the arbitration added them)
     const Reach rc = FAULTS ? reach_of(n, a.fa) : Reach{0u, 0xFFFFFFFFu};
     uint32_t p[4];
     bool live[4], coin[4];
@@ -138,11 +142,13 @@ __global__ __launch_bounds__(kSenderBlock) void round_monger_kernel(MongerArgs m
       if (!COUNT && a.k <= 4u) {  // one unrolled batch; with the planes live it costs the counter forms a wave
         draw_coins(m, n, 0u, a.k, coin);
         resolve_batch<TOPO, FAULTS>(a, a.fa, rc, n, b, d, 0u, a.k, p, live);
+        if (CONN) conn_resolve<TOPO, FAULTS>(m.conn, a, rc, n, b, d, 0u, p, live);
         hit = push_word<COUNT>(m, h, 0, p, live, coin, c);
       } else {
         for (uint32_t q = 0; q < nblk; ++q) {
           draw_coins(m, n, q, min(4u, a.k - 4u * q), coin);
           resolve_batch<TOPO, FAULTS>(a, a.fa, rc, n, b, d, q, min(4u, a.k - 4u * q), p, live);
+          if (CONN) conn_resolve<TOPO, FAULTS>(m.conn, a, rc, n, b, d, q, p, live);
           hit |= push_word<COUNT>(m, h, 0, p, live, coin, c);
         }
       }
@@ -153,6 +159,7 @@ __global__ __launch_bounds__(kSenderBlock) void round_monger_kernel(MongerArgs m
       for (uint32_t q = 0; q < nblk; ++q) {
         draw_coins(m, n, q, min(4u, a.k - 4u * q), coin);
         resolve_batch<TOPO, FAULTS>(a, a.fa, rc, n, b, d, q, min(4u, a.k - 4u * q), p, live);
+        if (CONN) conn_resolve<TOPO, FAULTS>(m.conn, a, rc, n, b, d, q, p, live);
         for (uint32_t w = 0; w < a.W; ++w) {
           const uint64_t woff = (uint64_t)w * a.N;
           const uint64_t hw = m.H[woff + s];
@@ -183,16 +190,22 @@ __global__ void monger_inject_kernel(uint64_t* S, uint64_t* H, uint64_t N, uint3
   if (!(old & bit)) atomicOr((unsigned long long*)&H[at], (unsigned long long)bit);  // held: not re-heated
 }
 
-template <bool ONE_WORD, bool TOPO, bool FAULTS>
+template <bool ONE_WORD, bool TOPO, bool FAULTS, bool CONN>
 void launch_count(const MongerArgs& m, uint32_t grid, hipStream_t st) {
-  if (m.C) round_monger_kernel<ONE_WORD, TOPO, FAULTS, true><<<grid, kSenderBlock, 0, st>>>(m);
-  else round_monger_kernel<ONE_WORD, TOPO, FAULTS, false><<<grid, kSenderBlock, 0, st>>>(m);
+  if (m.C) round_monger_kernel<ONE_WORD, TOPO, FAULTS, true, CONN><<<grid, kSenderBlock, 0, st>>>(m);
+  else round_monger_kernel<ONE_WORD, TOPO, FAULTS, false, CONN><<<grid, kSenderBlock, 0, st>>>(m);
+}
+
+template <bool ONE_WORD, bool TOPO, bool FAULTS>
+void launch_conn(const MongerArgs& m, uint32_t grid, hipStream_t st) {
+  if (m.conn.c) launch_count<ONE_WORD, TOPO, FAULTS, true>(m, grid, st);
+  else launch_count<ONE_WORD, TOPO, FAULTS, false>(m, grid, st);
 }
 
 template <bool ONE_WORD, bool TOPO>
 void launch_faults(const MongerArgs& m, uint32_t grid, hipStream_t st) {
-  if (m.a.fa.any()) launch_count<ONE_WORD, TOPO, true>(m, grid, st);
-  else launch_count<ONE_WORD, TOPO, false>(m, grid, st);
+  if (m.a.fa.any()) launch_conn<ONE_WORD, TOPO, true>(m, grid, st);
+  else launch_conn<ONE_WORD, TOPO, false>(m, grid, st);
 }
 
 }  // namespace

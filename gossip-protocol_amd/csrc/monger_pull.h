@@ -31,6 +31,7 @@ struct MongerPullArgs {
   bool topo;           // peers drawn from the rows (GOSSIP_FLAG_TOPO_PEERS) or from all N nodes
   uint64_t* C;         // [4][W][N] counter planes (monger.h), or null: the engine holds no counters
   uint32_t limit;      // 1..15
+  ConnArgs conn;       // connection limit: conn.c == 0 is the unlimited round (monger.h)
 };
 
 // The request pass: S_{t+1} and H_{t+1} with the replies in, the feedback in need / less, and the

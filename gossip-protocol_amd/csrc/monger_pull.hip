@@ -19,6 +19,9 @@
 // depend on the schedule.
 //
 // blind is a run-time value, as in monger.hip: both variants gather H_t[p].
+//
+// CONN: as in monger.hip, conn_resolve replaces the stage-0 peers of a batch
+// by the accepted targets; "delivered" then reads "accepted".  The unlimited forms keep their code.
 #include "monger_pull.h"
 
 #include "monger_close.h"
@@ -58,7 +61,7 @@ __device__ __forceinline__ uint64_t pull_word(const MongerPullArgs& m, uint64_t 
 // something hot.  A full node asks too: it cannot know that it lacks nothing, and its answer is
 // the feedback that cools the server.
 // ---------------------------------------------------------------------------
-template <bool ONE_WORD, bool TOPO, bool FAULTS>
+template <bool ONE_WORD, bool TOPO, bool FAULTS, bool CONN>
 __global__ __launch_bounds__(kSenderBlock) void round_monger_pull_kernel(MongerPullArgs m) {
   const RoundArgs& a = m.a;
   uint64_t msgs = 0;
@@ -81,6 +84,7 @@ __global__ __launch_bounds__(kSenderBlock) void round_monger_pull_kernel(MongerP
       if (asks) {
         for (uint32_t q = 0; q < nblk; ++q) {
           resolve_batch<TOPO, FAULTS>(a, a.fa, rc, n, b, d, q, min(4u, a.k - 4u * q), p, live);
+          if (CONN) conn_resolve<TOPO, FAULTS>(m.conn, a, rc, n, b, d, q, p, live);
           gain |= pull_word(m, sv, 0, p, live, &msgs);
         }
       }
@@ -97,6 +101,7 @@ __global__ __launch_bounds__(kSenderBlock) void round_monger_pull_kernel(MongerP
       // says no, and k probes replace k * W gathers.  Own words are read back: only this lane writes them
       for (uint32_t q = 0; q < nblk; ++q) {
         resolve_batch<TOPO, FAULTS>(a, a.fa, rc, n, b, d, q, min(4u, a.k - 4u * q), p, live);
+        if (CONN) conn_resolve<TOPO, FAULTS>(m.conn, a, rc, n, b, d, q, p, live);
         uint64_t bits[4];
         bool any = false;
 #pragma unroll
@@ -187,10 +192,16 @@ __global__ __launch_bounds__(kSenderBlock) void monger_hot_scan_kernel(const uin
   if (hot_nodes && cnt) atomicAdd((unsigned long long*)hot_nodes, (unsigned long long)cnt);
 }
 
+template <bool ONE_WORD, bool TOPO, bool FAULTS>
+void launch_conn(const MongerPullArgs& m, uint32_t grid, hipStream_t st) {
+  if (m.conn.c) round_monger_pull_kernel<ONE_WORD, TOPO, FAULTS, true><<<grid, kSenderBlock, 0, st>>>(m);
+  else round_monger_pull_kernel<ONE_WORD, TOPO, FAULTS, false><<<grid, kSenderBlock, 0, st>>>(m);
+}
+
 template <bool ONE_WORD, bool TOPO>
 void launch_faults(const MongerPullArgs& m, uint32_t grid, hipStream_t st) {
-  if (m.a.fa.any()) round_monger_pull_kernel<ONE_WORD, TOPO, true><<<grid, kSenderBlock, 0, st>>>(m);
-  else round_monger_pull_kernel<ONE_WORD, TOPO, false><<<grid, kSenderBlock, 0, st>>>(m);
+  if (m.a.fa.any()) launch_conn<ONE_WORD, TOPO, true>(m, grid, st);
+  else launch_conn<ONE_WORD, TOPO, false>(m, grid, st);
 }
 
 template <bool ONE_WORD>

@@ -22,6 +22,9 @@
 // are ORs: the result does not depend on the schedule.
 //
 // blind is a run-time value, as in monger_pull.hip: both variants gather H_t[p] and S_t[p].
+//
+// CONN: as in monger.hip, conn_resolve replaces the stage-0 peers of a batch
+// by the accepted targets; "delivered" then reads "accepted".  The unlimited forms keep their code.
 #include "monger_pushpull.h"
 
 #include "monger_close.h"
@@ -79,7 +82,7 @@ __device__ __forceinline__ void exchange_word(const MongerPushPullArgs& x, uint6
 // one end had something hot, once per exchange.  A full or cold node initiates too: it cannot know
 // that its peer has nothing for it, and what it holds is the feedback that cools the peer.
 // ---------------------------------------------------------------------------
-template <bool ONE_WORD, bool TOPO, bool FAULTS>
+template <bool ONE_WORD, bool TOPO, bool FAULTS, bool CONN>
 __global__ __launch_bounds__(kSenderBlock) void round_monger_pushpull_kernel(MongerPushPullArgs x) {
   const MongerPullArgs& m = x.m;
   const RoundArgs& a = m.a;
@@ -102,6 +105,7 @@ __global__ __launch_bounds__(kSenderBlock) void round_monger_pushpull_kernel(Mon
       Own o{0, 0, 0};
       for (uint32_t q = 0; q < nblk; ++q) {
         resolve_batch<TOPO, FAULTS>(a, a.fa, rc, n, b, d, q, min(4u, a.k - 4u * q), p, live);
+        if (CONN) conn_resolve<TOPO, FAULTS>(m.conn, a, rc, n, b, d, q, p, live);
         exchange_word(x, sv, hv, 0, p, live, o, &msgs);
       }
       or_nonzero(&x.gain[s], o.gain);
@@ -114,6 +118,7 @@ __global__ __launch_bounds__(kSenderBlock) void round_monger_pushpull_kernel(Mon
       const bool own_hot = (m.hotmap[s >> 6] >> (s & 63u)) & 1ull;
       for (uint32_t q = 0; q < nblk; ++q) {
         resolve_batch<TOPO, FAULTS>(a, a.fa, rc, n, b, d, q, min(4u, a.k - 4u * q), p, live);
+        if (CONN) conn_resolve<TOPO, FAULTS>(m.conn, a, rc, n, b, d, q, p, live);
         if (!own_hot) {
           uint64_t bits[4];
 #pragma unroll
@@ -188,10 +193,16 @@ __global__ __launch_bounds__(kSenderBlock) void monger_pushpull_close_kernel(Mon
   if (hot_nodes) atomicAdd((unsigned long long*)m.hot_nodes, (unsigned long long)hot_nodes);
 }
 
+template <bool ONE_WORD, bool TOPO, bool FAULTS>
+void launch_conn(const MongerPushPullArgs& x, uint32_t grid, hipStream_t st) {
+  if (x.m.conn.c) round_monger_pushpull_kernel<ONE_WORD, TOPO, FAULTS, true><<<grid, kSenderBlock, 0, st>>>(x);
+  else round_monger_pushpull_kernel<ONE_WORD, TOPO, FAULTS, false><<<grid, kSenderBlock, 0, st>>>(x);
+}
+
 template <bool ONE_WORD, bool TOPO>
 void launch_faults(const MongerPushPullArgs& x, uint32_t grid, hipStream_t st) {
-  if (x.m.a.fa.any()) round_monger_pushpull_kernel<ONE_WORD, TOPO, true><<<grid, kSenderBlock, 0, st>>>(x);
-  else round_monger_pushpull_kernel<ONE_WORD, TOPO, false><<<grid, kSenderBlock, 0, st>>>(x);
+  if (x.m.a.fa.any()) launch_conn<ONE_WORD, TOPO, true>(x, grid, st);
+  else launch_conn<ONE_WORD, TOPO, false>(x, grid, st);
 }
 
 template <bool ONE_WORD>

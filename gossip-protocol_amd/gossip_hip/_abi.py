@@ -79,6 +79,7 @@ SIGNATURES = [
     ("set_faults", C.c_int, [P, C.c_uint32, C.c_uint32]),
     ("set_monger", C.c_int, [P, C.c_uint32, C.c_uint32]),
     ("set_monger_limit", C.c_int, [P, C.c_uint32]),
+    ("set_monger_connections", C.c_int, [P, C.c_uint32, C.c_uint32]),
     ("set_param", C.c_int, [P, C.c_char_p, C.c_double]),
     ("step", C.c_int, [P, C.c_uint32, C.POINTER(RoundStats), U64P, U32P]),
     ("partial_len", C.c_uint64, [P]),
@@ -123,12 +124,14 @@ SIGNATURES = [
     ("read_hot_shard", C.c_int, [P, U64P, C.c_uint64]),
     ("read_monger_counts", C.c_int, [P, U64P, C.c_uint64]),
     ("monger_hot_nodes", C.c_int, [P, U64P]),
+    ("monger_connections", C.c_int, [P, U64P]),
     ("read_versions", C.c_int, [P, C.c_uint64, U32P, C.c_uint32, U32P]),
     ("shard_range", C.c_int, [P, U64P, U64P]),
     ("state_hash", C.c_int, [P, U64P]),
     ("round_index", C.c_uint32, [P]),
     ("peer", C.c_uint32, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("topo_peer_index", C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("monger_conn_words", C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, U32P]),
     ("philox_device", C.c_int, [P, U32P, U32P, U32P, C.c_uint32]),
     ("kernel_time", C.c_int, [P, C.c_uint32, C.POINTER(C.c_double), U64P]),
     ("reset_timing", C.c_int, [P]),
@@ -147,7 +150,8 @@ SIGNATURES = [
 # entry points of the HIP engine only (the oracle library exports the rest under "oracle_")
 ENGINE_ONLY = {"comm_unique_id", "comm_init_rank", "group_create", "group_destroy", "group_engine", "group_transport",
                "group_step", "group_last_error", "set_monger", "read_hot_shard", "set_monger_limit",
-               "read_monger_counts", "monger_hot_nodes"}
+               "read_monger_counts", "monger_hot_nodes", "set_monger_connections", "monger_connections",
+               "monger_conn_words"}
 
 
 def bind(lib: C.CDLL, prefix: str, names=None) -> C.CDLL:

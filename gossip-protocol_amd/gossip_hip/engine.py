@@ -514,6 +514,21 @@ class Engine(AbiEngine):
         self._check(self._fn("monger_hot_nodes")(self._h, C.byref(out)))
         return out.value
 
+    def set_monger_connections(self, conn_limit: int, hunt_limit: int = 0):
+        """Any mongering flag, for the rounds that follow: a node accepts at most
+        conn_limit (1..8) incoming connections per round, and the initiator of a refused edge tries up
+        to hunt_limit (0..15) further peers.  0, the value after create, is no limit (hunt_limit must
+        then be 0): the engine runs as if the call did not exist."""
+        self._check(self._fn("set_monger_connections")(self._h, C.c_uint32(int(conn_limit)), C.c_uint32(int(hunt_limit))))
+
+    def connections(self) -> dict:
+        """Any mongering flag: what the last round did under set_monger_connections' limit — attempts
+        over all stages (lost ones included), accepted edges, edges refused in the last stage, and hunt
+        attempts.  All zero before the first round, after reset and without a limit."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._fn("monger_connections")(self._h, out))
+        return dict(attempts=out[0], accepted=out[1], refused=out[2], hunts=out[3])
+
     def kernel_time(self, which: int):
         ms, n = C.c_double(), C.c_uint64()
         self._check(self._fn("kernel_time")(self._h, C.c_uint32(which), C.byref(ms), C.byref(n)))
@@ -654,6 +669,16 @@ class Group:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def monger_conn_words(seed: int, node: int, round_: int, stage: int, j: int):
+    """(priority word, hunt word) of edge j of node in round_ at a stage of the connection
+    arbitration, as the kernels draw them (host copy of the device function)."""
+    out = (C.c_uint32 * 2)()
+    rc = load_library().gossip_monger_conn_words(seed, node, round_, stage, j, out)
+    if rc:
+        raise GossipError(rc, "gossip_monger_conn_words: stage <= 15 and j <= 63")
+    return int(out[0]), int(out[1])
 
 
 def peer(seed: int, n_nodes: int, node: int, round_: int, j: int) -> int:

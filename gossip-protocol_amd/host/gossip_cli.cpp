@@ -24,6 +24,11 @@
 //              [--monger-limit M]   with --monger: the counter rule (gossip_set_monger_limit), a
 //                               rumor cools once M (1..15) counted contacts have passed the coin;
 //                               the paper's pure counter is --monger 1 --monger-limit M
+//              [--conn-limit C [--hunt H]]   with --monger: a node accepts at most C (1..8) incoming
+//                               connections per round, and the initiator of a refused edge tries up
+//                               to H (0..15) further peers (gossip_set_monger_connections); the line
+//                               then carries both values and the last round's attempts, accepted and
+//                               refused edges and hunts
 //              [--shards G [--devices d0,d1,...]]   G shards in this process, every round
 //                                                   driven by the library (gossip_group_*:
 //                                                   RCCL over distinct devices, else copies)
@@ -56,6 +61,7 @@ int main(int argc, char** argv) {
   double monger = -1.0;  // < 0: off
   uint32_t monger_limit = 1;
   bool limit_given = false;
+  uint32_t conn_limit = 0, hunt = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
@@ -73,6 +79,8 @@ int main(int argc, char** argv) {
       monger_limit = (uint32_t)std::strtoul(next(), nullptr, 0);
       limit_given = true;
     }
+    else if (a == "--conn-limit") conn_limit = (uint32_t)std::strtoul(next(), nullptr, 0);
+    else if (a == "--hunt") hunt = (uint32_t)std::strtoul(next(), nullptr, 0);
     else if (a == "--shards") shards = (uint32_t)std::strtoul(next(), nullptr, 0);
     else if (a == "--devices") {
       for (char* p = next(); *p;) {
@@ -115,6 +123,10 @@ int main(int argc, char** argv) {
   }
   if (limit_given && (monger < 0 || monger_limit < 1 || monger_limit > 15)) {
     std::fprintf(stderr, "--monger-limit M (1 <= M <= 15) goes with --monger\n");
+    return 2;
+  }
+  if ((conn_limit || hunt) && (monger < 0 || conn_limit < 1 || conn_limit > 8 || hunt > 15)) {
+    std::fprintf(stderr, "--conn-limit C (1 <= C <= 8) goes with --monger, --hunt H (0 <= H <= 15) with --conn-limit\n");
     return 2;
   }
   cfg.mode = base == "push" ? GOSSIP_MODE_PUSH : base == "pull" ? GOSSIP_MODE_PULL
@@ -177,6 +189,8 @@ int main(int argc, char** argv) {
       return die(e, "gossip_set_monger", rc);
     if (limit_given)
       if (int rc = gossip_set_monger_limit(e, monger_limit)) return die(e, "gossip_set_monger_limit", rc);
+    if (conn_limit)
+      if (int rc = gossip_set_monger_connections(e, conn_limit, hunt)) return die(e, "gossip_set_monger_connections", rc);
     infected.resize(st.size() * rumors);
   }
   for (uint32_t run = 0; run < runs; ++run) {
@@ -204,14 +218,23 @@ int main(int argc, char** argv) {
         worst = miss > worst ? miss : worst;
         sum += miss;
       }
+      char conn[192] = "";  // --conn-limit: what the last round did under the limit
+      if (conn_limit) {
+        uint64_t cn[4];
+        if (int rc = gossip_monger_connections(e, cn)) return die(e, "gossip_monger_connections", rc);
+        std::snprintf(conn, sizeof conn, ",\"conn_limit\":%u,\"hunt\":%u,\"last_attempts\":%llu,\"last_accepted\":%llu,"
+                      "\"last_refused\":%llu,\"last_hunts\":%llu",
+                      conn_limit, hunt, (unsigned long long)cn[0], (unsigned long long)cn[1], (unsigned long long)cn[2],
+                      (unsigned long long)cn[3]);
+      }
       std::printf("{\"run\":%u,\"mode\":\"%s\",\"monger\":%.6f,\"blind\":%u,\"monger_limit\":%u,\"nodes\":%llu,"
                   "\"rumors\":%u,"
                   "\"rounds\":%u,\"quiescent\":%u,\"converged\":%u,\"residue_max\":%llu,\"residue_mean\":%.3f,"
-                  "\"messages\":%llu,\"messages_per_node\":%.4f,\"seconds\":%.6f,\"state_hash\":\"0x%016llx\"}\n",
+                  "\"messages\":%llu,\"messages_per_node\":%.4f,\"seconds\":%.6f,\"state_hash\":\"0x%016llx\"%s}\n",
                   run, mode.c_str(), monger, blind ? 1u : 0u, monger_limit, (unsigned long long)nodes, rumors, done,
                   done && (by_hot ? hot == 0 : last.messages == 0) ? 1u : 0u, last.converged, (unsigned long long)worst,
                   (double)sum / rumors, (unsigned long long)messages, (double)messages / (double)nodes, s,
-                  (unsigned long long)last.state_hash);
+                  (unsigned long long)last.state_hash, conn);
       continue;
     }
     std::printf("{\"run\":%u,\"mode\":\"%s\",\"nodes\":%llu,\"rumors\":%u,\"rounds\":%u,\"converged\":%u,"

@@ -317,6 +317,17 @@ func (e *Engine) SetMongerLimit(limit uint32) error {
 	return e.call(C.gossip_set_monger_limit(e.h, C.uint32_t(limit)))
 }
 
+// SetMongerConnections sets the connection limit and the hunt limit of an engine created with
+// FlagMonger, FlagMongerPull or FlagMongerPushPull, for the rounds that follow (DESIGN.md §2.17):
+// a node accepts at most connLimit (1..8) incoming connections per round, and the initiator of a
+// refused edge tries up to huntLimit (0..15) further peers.  0, the value after New, is no limit
+// (huntLimit must then be 0).
+func (e *Engine) SetMongerConnections(connLimit, huntLimit uint32) error {
+	e.mu.Lock()
+	defer e.mu.Unlock()
+	return e.call(C.gossip_set_monger_connections(e.h, C.uint32_t(connLimit), C.uint32_t(huntLimit)))
+}
+
 // SetParam sets a tuning / path-selection knob (gossip_set_param); results never change.
 func (e *Engine) SetParam(name string, value float64) error {
 	e.mu.Lock()
@@ -547,6 +558,26 @@ func (e *Engine) HotNodes() (uint64, error) {
 	return uint64(out), nil
 }
 
+// Connections is what one round did under SetMongerConnections' limit.
+type Connections struct {
+	Attempts uint64 // over all stages, lost ones included
+	Accepted uint64
+	Refused  uint64 // in the last stage
+	Hunts    uint64 // attempts of the stages after the first
+}
+
+// MongerConnections reports on the last round run; all zero before the first round, after Reset
+// and without a limit.
+func (e *Engine) MongerConnections() (Connections, error) {
+	e.mu.Lock()
+	defer e.mu.Unlock()
+	var out [4]C.uint64_t
+	if rc := C.gossip_monger_connections(e.h, &out[0]); rc != 0 {
+		return Connections{}, e.fail(rc)
+	}
+	return Connections{uint64(out[0]), uint64(out[1]), uint64(out[2]), uint64(out[3])}, nil
+}
+
 // ReadVersions returns one node's K versions and its alive flag (ANTIENTROPY).
 func (e *Engine) ReadVersions(node uint64) ([]uint32, bool, error) {
 	e.mu.Lock()
@@ -656,6 +687,15 @@ func Peer(seed, nodes uint64, node, round, j uint32) uint32 {
 // j-th peer under FlagTopoPeers, exactly as the kernels compute it (0 for an empty row).
 func TopoPeerIndex(seed uint64, degree, node, round, j uint32) uint32 {
 	return uint32(C.gossip_topo_peer_index(C.uint64_t(seed), C.uint32_t(degree), C.uint32_t(node), C.uint32_t(round), C.uint32_t(j)))
+}
+
+// MongerConnWords is the priority word and the hunt word of edge j (below 64) of node in round at a
+// stage (at most 15) of the connection arbitration, exactly as the kernels draw them; ok is false out
+// of range.
+func MongerConnWords(seed uint64, node, round, stage, j uint32) (prio, hunt uint32, ok bool) {
+	var out [2]C.uint32_t
+	rc := C.gossip_monger_conn_words(C.uint64_t(seed), C.uint32_t(node), C.uint32_t(round), C.uint32_t(stage), C.uint32_t(j), &out[0])
+	return uint32(out[0]), uint32(out[1]), rc == 0
 }
 
 // locked runs one cgo call under e.mu (one engine is not thread-safe, include/gossip.h).

@@ -367,6 +367,24 @@ int gossip_set_monger(gossip_engine_t* eng, uint32_t cool, uint32_t blind);
  * GOSSIP_FLAG_MONGER_PUSHPULL likewise: the counts are those of both ends of an exchange. */
 int gossip_set_monger_limit(gossip_engine_t* eng, uint32_t limit);
 
+/* Connection limits and hunting (Demers et al. §1.4), for the rounds that follow, on an
+ * engine created with GOSSIP_FLAG_MONGER, _MONGER_PULL or _MONGER_PUSHPULL.  conn_limit = c in 1..8: a node
+ * accepts at most c incoming connections per round; of the edges delivered to it, it takes the c with the
+ * smallest priority (a Philox word per edge, stream tag 6; ties by initiator, then edge), whatever the
+ * order they arrive in.  hunt_limit = h in 0..15: the initiator of a refused edge tries up to h further
+ * peers, one per stage, each drawn as the first one was (over the rows with GOSSIP_FLAG_TOPO_PEERS), with
+ * replacement.  A place taken in an earlier stage is never lost to a later one.  An accepted edge is a
+ * delivered edge of the round with the peer that accepted it; an edge refused in the last stage is treated
+ * exactly as a lost one.  The loss draw belongs to the edge, not to the attempt: a lost edge never contends
+ * and does not hunt, and neither does an attempt whose target lies outside the initiator's partition block.
+ * Statistics: GOSSIP_FLAG_MONGER counts every attempt as a message, hunts and lost ones included; the other
+ * two flags keep their definitions with "delivered" read as "accepted".  conn_limit = 0 (the value after
+ * create): no limit, the engine runs as if the call did not exist; hunt_limit must then be 0.  The first
+ * call with conn_limit > 0 allocates 8 * conn_limit bytes per node, kept from then on; gossip_reset keeps
+ * both values.  GOSSIP_ESTATE on an engine created with none of the flags, GOSSIP_EINVAL out of range,
+ * GOSSIP_ENOMEM when the buffers cannot be allocated (engine and values then unchanged). */
+int gossip_set_monger_connections(gossip_engine_t* eng, uint32_t conn_limit, uint32_t hunt_limit);
+
 /* Runs rounds until converged (FLOOD also: a round that sends nothing) or max_rounds
  * rounds have run.  GOSSIP_FLAG_MONGER: until the first round that sends nothing (that round is
  * reported) or max_rounds, and not until converged; on return gossip_round_index and the state
@@ -432,6 +450,13 @@ int gossip_read_monger_counts(gossip_engine_t* eng, uint64_t* out, uint64_t n_wo
  * rule of GOSSIP_FLAG_MONGER_PULL and _MONGER_PUSHPULL with this call: the partial vector does not carry the
  * number.  GOSSIP_ESTATE on an engine created with none of the flags, GOSSIP_EINVAL for a null argument. */
 int gossip_monger_hot_nodes(gossip_engine_t* eng, uint64_t* out);
+/* gossip_set_monger_connections: what the last round did under the limit, out[4] = {attempts over all
+ * stages (lost ones included), edges accepted, edges refused in the last stage, hunt attempts (stages
+ * >= 1)}.  With edges = the round's k per initiating node and lost = the edges closed by a loss draw or a
+ * partition, edges = accepted + lost + refused and attempts = edges + hunts in every round.  All zero
+ * before the first round, after gossip_reset, after a round without a limit and while conn_limit is 0.
+ * GOSSIP_ESTATE on an engine created with none of the flags, GOSSIP_EINVAL for a null argument. */
+int gossip_monger_connections(gossip_engine_t* eng, uint64_t* out);
 /* ANTIENTROPY readout: the K versions of one node (owned by this shard), and its alive flag. */
 int gossip_read_versions(gossip_engine_t* eng, uint64_t node, uint32_t* out, uint32_t ncomp, uint32_t* alive);
 /* ANTIENTROPY readout of every owned row: out[i * K + c] for owned node lo + i. */
@@ -450,6 +475,12 @@ uint32_t gossip_peer(uint64_t seed, uint64_t n_nodes, uint32_t node, uint32_t ro
 /* GOSSIP_FLAG_TOPO_PEERS: the index i_j into a row of `degree` entries that node draws in round
  * for its j-th peer, exactly as the kernels compute it (host code, parity probe); 0 for degree 0. */
 uint32_t gossip_topo_peer_index(uint64_t seed, uint32_t degree, uint32_t node, uint32_t round, uint32_t j);
+/* gossip_set_monger_connections: out[2] = {priority word, hunt word} of edge j < 64 of node in round at
+ * stage <= 15, exactly as the kernels compute them (host code, parity probe): words j & 3 of
+ * Philox4x32-10({node, round, 6 | stage << 16, j >> 2}, seed) and of the same with counter word 3 =
+ * 16 + (j >> 2).  The priority is the word's top 22 bits; the hunt word is mapped to a peer as
+ * gossip_peer / gossip_topo_peer_index map theirs.  GOSSIP_EINVAL for a null out, stage > 15 or j > 63. */
+int gossip_monger_conn_words(uint64_t seed, uint32_t node, uint32_t round, uint32_t stage, uint32_t j, uint32_t* out);
 
 /* Device-side Philox4x32-10 of n counters (known-answer tests): ctr4/out4 hold
  * 4*n words, key2 = 2 words. Runs on the engine's device. */

@@ -11,9 +11,10 @@ measure that one instead.  --pull runs a PULL engine with GOSSIP_FLAG_MONGER_PUL
 is then the request and the close pass, a run ends with the first round that leaves no node hot, and
 the messages are the replies that carried a rumor.  --pushpull runs a PUSHPULL engine with
 GOSSIP_FLAG_MONGER_PUSHPULL (§2.16, §3.14): the same timers and stop rule, and the messages are the exchanges
-in which an end was hot.
+in which an end was hot.  --conn-limit C [--hunt H] sets gossip_set_monger_connections (§2.17, §3.15): timer 0
+then also covers the arbitration, and the line carries the attempts, accepted and refused edges and hunts per node.
 Usage: monger_probe.py [--log2 24] [--cool 0.5|always] [--limit 0] [--planes] [--blind] [--pull | --pushpull] [--runs 3]
-                       [--pkg DIR [--build NAME]]"""
+                       [--conn-limit 0 [--hunt 0]] [--pkg DIR [--build NAME]]"""
 import argparse
 import json
 import os
@@ -27,6 +28,8 @@ ap.add_argument("--blind", action="store_true")
 ap.add_argument("--planes", action="store_true")
 ap.add_argument("--pull", action="store_true")
 ap.add_argument("--pushpull", action="store_true")
+ap.add_argument("--conn-limit", type=int, default=0)
+ap.add_argument("--hunt", type=int, default=0)
 ap.add_argument("--runs", type=int, default=3)
 ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED0003)
 ap.add_argument("--build", default="this tree", help="a name for the measured build, echoed in the JSON line")
@@ -60,15 +63,21 @@ with Engine(N, R, "pushpull" if a.pushpull else "pull" if a.pull else "push", K,
         e.set_monger_limit(1)
     if a.limit:
         e.set_monger_limit(a.limit)
+    if a.conn_limit:   # (never called without one: a build from before the call runs the rest)
+        e.set_monger_connections(a.conn_limit, a.hunt)
     for rep in range(a.runs + 1):
         e.reset()
         e.inject_random()
         per_round = []
+        conn = dict(attempts=0, accepted=0, refused=0, hunts=0)
         for _ in range(CAP):
             e.reset_timing()
             res = e.step(1)
             t0, t1 = e.kernel_time(0)[0] * 1e3, e.kernel_time(1)[0] * 1e3
             per_round.append((res.stats[0]["messages"], t0, t1, res.stats[0]["full_nodes"], res.infected[0]))
+            if a.conn_limit:
+                for key, v in e.connections().items():
+                    conn[key] += v
             if (e.hot_nodes() if by_hot else res.stats[0]["messages"]) == 0:
                 break
         if rep:
@@ -88,7 +97,8 @@ def us(idx, col):
 
 
 print(json.dumps({
-    "build": a.build, "pull": a.pull, "pushpull": a.pushpull, "nodes": N, "rumors": R, "fanout": K, "cool": a.cool, "blind": a.blind, "limit": a.limit, "planes": a.planes,
+    "build": a.build, "conn_limit": a.conn_limit, "hunt": a.hunt, "conn_per_node": {k: v / N for k, v in conn.items()},
+    "pull": a.pull, "pushpull": a.pushpull, "nodes": N, "rumors": R, "fanout": K, "cool": a.cool, "blind": a.blind, "limit": a.limit, "planes": a.planes,
     "rounds": len(last), "residue_nodes": [min(miss), max(miss)], "residue_share": [min(miss) / N, max(miss) / N],
     "full_nodes": last[-1][3], "messages_per_node": sum(p[0] for p in last) / N,
     "peak_round": peak, "peak_messages": last[peak][0],

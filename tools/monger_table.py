@@ -1,6 +1,6 @@
-"""Rumor mongering's residue against its traffic, the three tables
-of Demers et al., "Epidemic algorithms for replicated database maintenance", and a fourth for push-pull,
-on the GPU engine: one rumor injected at node 0 of N nodes, uniform peers, one run to quiescence per row.
+"""Rumor mongering's residue against its traffic, the three
+tables of Demers et al., "Epidemic algorithms for replicated database maintenance", a fourth for push-pull
+and a fifth under a connection limit, on the GPU engine: one rumor injected at node 0 of N nodes, uniform peers, one run to quiescence per row.
 
   feedback + counter   cool = 2^32 - 1 (a coin that fails with probability 2^-32), limit = m:
                        a sender loses interest after m pushes to peers that knew the rumor
@@ -13,6 +13,10 @@ on the GPU engine: one rumor injected at node 0 of N nodes, uniform peers, one r
   + counter            send the rumor while hot, and each loses interest after m rounds in which a
                        partner held the rumor and none lacked it; the messages are the exchanges in
                        which an end was hot
+  connection limit     the three feedback + counter rows at limit = m = 2 when a node accepts one
+                       connection per round (gossip_set_monger_connections, c = 1) and a refused
+                       initiator hunts for h = 0, 1 or 15 further peers, beside the unlimited engine;
+                       push counts every attempt as a message
 
 Per m it prints the residue (the share of nodes that never heard the rumor), the messages per node
 and the rounds to quiescence (the quiescent round included).  The paper's figures (N = 1000, its own
@@ -33,11 +37,13 @@ CAP = 4096
 KINDS = {"push": FLAG_MONGER, "pull": FLAG_MONGER_PULL, "pushpull": FLAG_MONGER_PUSHPULL}
 
 
-def row(n, k, seed, cool, blind, limit, mode="push"):
+def row(n, k, seed, cool, blind, limit, mode="push", conn=None):
     with Engine(n, 1, mode, k, seed, flags=KINDS[mode]) as e:
         e.set_monger(cool, blind)
         if limit > 1:
             e.set_monger_limit(limit)
+        if conn:
+            e.set_monger_connections(*conn)
         e.inject(0, 0)
         res = e.step(CAP)
         quiet = e.hot_nodes() == 0 if mode != "push" else res.stats[-1]["messages"] == 0
@@ -64,6 +70,12 @@ def main():
         for m in range(1, a.max_m + 1):
             s, msgs, rounds = row(n, a.fanout, a.seed, *args(m))
             print(f"| {m} | {s:.5f} | {msgs:.3f} | {rounds} |", flush=True)
+    print("\nconnection limit c = 1 (feedback, counter, cool = 2^32 - 1, limit = 2)\n"
+          "| mode | hunts | residue | messages per node | rounds |\n|---|---|---|---|---|")
+    for mode in KINDS:
+        for conn in (None, (1, 0), (1, 1), (1, 15)):
+            s, msgs, rounds = row(n, a.fanout, a.seed, ALWAYS, False, 2, mode, conn)
+            print(f"| {mode} | {'unlimited' if conn is None else conn[1]} | {s:.5f} | {msgs:.3f} | {rounds} |", flush=True)
 
 
 if __name__ == "__main__":
